@@ -2,7 +2,7 @@
 """bench.py -- the headline measurement (BASELINE.json: "GB/s text scanned + matches/s,
 regexdna 50M-line input, 1/2/4/8 MI355X").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload regexdna|literal|complex|jrep]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload regexdna|literal|complex|jrep] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -27,12 +27,19 @@ The headline step is ONE kernel over the text for all nine patterns: regexdna as
 sample/regexdna.cc:65), and for counts plane_count scans, classifies its candidates by table lookup and counts
 (rj_multi_set_counts_only; plane_count.hip), a small kernel on the object's own stream adds the workgroups' rows up.
 `--span-lists` / `step_variants_ms.span_lists`: round 4's loop, which lays out every pattern's (begin, end) list
-(plane_scan + classify_shared_multi + offsets_gather_check_multi).  Besides the contract fields the line carries
+(plane_scan + classify_shared_multi + offsets_gather_check_multi).
+
+A plain run sets up, runs the step loop untimed (--settle-ms, then W warm-up steps), times the K steps and prints the
+line; `--dump-outputs DIR` then writes what the last timed step computed (regexdna: matches_per_pass.npy, the nine
+counts, and match_bounds.npy, per pattern the first / last match; literal / complex: spans.npy; jrep:
+files_with_matches.npy, output_bytes.npy).  Everything else -- the entries below from cpu_baseline on, the same-run
+read-only ceiling, the parity checks, the multi-rank latency -- runs only with `--full`.  Besides the contract fields
+the line carries
   physical_GBps / step_frac -- n / t of the step: every text byte crosses the HBM interface once per step
   roofline      -- the dominant kernel (plane_count<ExactShape<2>>): the text's bytes (1 byte read per text byte and pass,
                    SURVEY.md section 8d) / the launch's average duration from HIP events on the run's stream,
                    traffic = FETCH_SIZE x 2 per launch from profiles/pmc_traffic.json; read_only_ceiling /
-                   frac_of_ceiling: against a kernel that only reads the same bytes, measured in this run (`hbm_ceiling`;
+                   frac_of_ceiling (--full): against a kernel that only reads the same bytes, measured in this run (`hbm_ceiling`;
                    since round 6 with non-temporal loads, as the scans load: 6.9 TB/s; `default_policy_GB_per_s` beside it
                    is what rounds 1-5 quoted, 6.0-6.3)
   roofline_valu -- the same launch against the VALU peak (SQ_INSTS_VALU per byte from profiles/)
@@ -118,6 +125,11 @@ def parse_args():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); gloo only for "
                     "functional tests of the multi-rank path on a 1-GPU box together with --same-device")
     ap.add_argument("--same-device", action="store_true", help="testing only: every rank uses cuda:0")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the extras, the CPU baseline, the same-run "
+                    "read-only ceiling and the parity checks (--no-extra / --no-big / --no-cpu-baseline trim it); without it a run "
+                    "sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps: what the last timed step computed, as DIR/<name>.npy "
+                    "(float64; a seeded sample when larger than 64 MB in all)")
     return ap.parse_args()
 
 
@@ -259,6 +271,23 @@ def timed(c, args, step, finish=None):
         c.dist.all_reduce(tmax, op=c.dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     return elapsed, last
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float64 (exact for the counts and byte offsets here); when the
+    whole would pass 64 MB, each array keeps a fixed, seeded sample of its rows (sorted, so runs compare row for row)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+            a = a[np.sort(np.random.default_rng(12345).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def base_line(args, c, metric, value, elapsed, config):
@@ -408,6 +437,7 @@ def run_regexdna(args, c):
         def collect(j, record):
             local = multis[j].finish()
             fly["busy"][j] = False
+            fly["last"] = multis[j]                       # (the object of the newest result: --dump-outputs reads its bounds)
             if record and timed[j]:
                 times.append(multis[j].scan_ms())         # ONE launch scans the nine patterns (plane_scan)
             if exchange is None:
@@ -436,6 +466,7 @@ def run_regexdna(args, c):
                     res = collect(j, True)
             return res
 
+        step.fly = fly
         return step, drain, times
 
     # Two steps in flight (rj_multi_start / rj_multi_finish on two rj_multi objects used alternately): while the host
@@ -495,12 +526,18 @@ def run_regexdna(args, c):
                                                  "counts_equal_headline": cp == counts,
                                                  "headline_ms_per_step_in_this_process": round(elapsed / args.steps * 1e3, 4)}}))
         return None, False
+    # --dump-outputs: what a caller of the timed path receives from its last step -- the nine counts and, per pattern, the
+    # (first begin, first end, last begin, last end) that rj_multi leaves (-1 without a match; this rank's shard)
+    dump = {"matches_per_pass": counts}
+    last_multi = getattr(step, "fly", {}).get("last")
+    if last_multi is not None:
+        dump["match_bounds"] = [[-1] * 4 if b is None else list(to_global(b)) for b in last_multi.bounds(stream)]
     # Absolute match latency at N ranks (BASELINE's north star: "GB/s scan throughput and absolute match latency reported
     # at 1/2/4/8 GPUs"): ten synchronous steps -- one rj_multi_run over the rank's shard, then the exchange -- timed on every
     # rank, the shard's run and the exchange apart; rank 0 reports every rank's medians.  (A step of the timed loop above
     # overlaps these with the next step's kernels; this is what ONE call costs.)
     per_rank = None
-    if use_multi and world > 1:
+    if use_multi and world > 1 and args.full:
         lat_multi = rejit_amd.MultiScan(progs)
         lat_multi.set_mode(0)
         if counts_headline:
@@ -565,9 +602,12 @@ def run_regexdna(args, c):
     if use_multi:
         # the dominant kernel: plane_scan reads every text byte ONCE for all nine patterns: algorithmic bytes per
         # launch = text bytes (for a fused pass quote n / t_fused, never 9 n / t_fused, against HBM)
-        assert multi_sep.run(text_ptr, n_local, stream=stream, own_begin=own_lo, own_end=own_hi) == (counts if world == 1 else multi_sep.run(text_ptr, n_local, stream=stream, own_begin=own_lo, own_end=own_hi))
-        one_pass = multi_sep.how == 1
-        ceiling = hbm_ceiling(text_ptr, n_local, stream) if rank == 0 else None
+        # (--full: the synchronous call checked against the loop and the same-run read-only ceiling, runs of their own)
+        one_pass, ceiling = last_multi is not None and last_multi.how == 1, None
+        if args.full:
+            assert multi_sep.run(text_ptr, n_local, stream=stream, own_begin=own_lo, own_end=own_hi) == (counts if world == 1 else multi_sep.run(text_ptr, n_local, stream=stream, own_begin=own_lo, own_end=own_hi))
+            one_pass = multi_sep.how == 1
+            ceiling = hbm_ceiling(text_ptr, n_local, stream) if rank == 0 else None
         kernel_name = ("plane_count<ExactShape<2>> (one pass, nine patterns: scan + classification + counts)" if counts_headline else
                        "plane_scan<2> (one pass, nine patterns)" if one_pass else "scan kernels of rj_multi_run")
         out["roofline"] = hbm_roofline(kernel_name, own_bytes, avg_scan_ms,
@@ -599,7 +639,7 @@ def run_regexdna(args, c):
                                     "note": "ops_per_text_byte from " + ops_source + " (a separate PMC pass over the same kernel; not typed in by hand)"}
     else:
         out["roofline"] = hbm_roofline("scan_windows<2,NIB>", own_bytes, avg_scan_ms, None, len(scan_ms))
-    extras = rank == 0 and world == 1 and not args.no_extra
+    extras = rank == 0 and world == 1 and args.full and not args.no_extra
 
     call_times = {}
 
@@ -816,7 +856,7 @@ def run_regexdna(args, c):
         out["overlapped"] = {"pattern_threads": 3, "value": round(scanned / e3 / 1e9, 3), "unit": "GB/s",
                              "ms_per_step": round(e3 / args.steps * 1e3, 4)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # bounded sample taken from the lower-case (matching) part of the text: the first 20 %
         # is the upper-case ALU repeat, which no pattern can match
         # the all-core leg scans the WHOLE text (9 x 500 MB = 4.5 GB, disjoint slices); the one-core leg a 64 MiB
@@ -840,7 +880,7 @@ def run_regexdna(args, c):
 
     del text
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         fx = fullsize_fixture()
         if fx and "c3" in fx and fx["c3"]["fasta_n"] == args.fasta_n:
             want = [p["digest"]["count"] for p in fx["c3"]["patterns"]]
@@ -905,6 +945,7 @@ def run_regexdna(args, c):
                                                         ceiling=hbm_ceiling(big.data_ptr(), nb, stream))}
         del big, m2, m0, mc
         torch.cuda.empty_cache()
+    out["_dump"] = dump
     return out, extras
 
 
@@ -1427,6 +1468,9 @@ def run_single_pattern(args, c, which):
     out["matches"] = int(total)
     a_ms = sum(ms) / max(len(ms), 1)
     out["roofline"] = hbm_roofline("scan_windows<1>", own_bytes, a_ms, None, len(ms))
+    # --dump-outputs: the job's (begin, end) spans as gathered on rank 0, global offsets
+    if rank == 0:
+        out["_dump"] = {"spans": gathered.cpu().numpy().reshape(-1, 2)}
     return out
 
 
@@ -1499,6 +1543,10 @@ def run_jrep(args, c):
     out["roofline"] = {"bound": "hbm", "note": "PCIe- and host-bound end to end; the device pass is the regexdna / literal kernel",
                        "achieved": round(job_bytes * args.steps / elapsed / 1e9 / max(world, 1), 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                        "frac": round(job_bytes * args.steps / elapsed / 1e9 / max(world, 1) / HBM_PEAK_GBS, 5), "traffic": None}
+    # --dump-outputs: the files with matches and the formatted output (file:line:text) as its bytes
+    if rank == 0:
+        import numpy as np
+        out["_dump"] = {"files_with_matches": [job_hits], "output_bytes": np.frombuffer(whole, dtype=np.uint8)}
     return out
 
 
@@ -1722,6 +1770,9 @@ def main():
         out = run_single_pattern(args, c, args.workload)
     else:
         out = run_jrep(args, c)
+    dump = out.pop("_dump", None)
+    if c.rank == 0 and args.dump_outputs and dump is not None:
+        dump_outputs(args.dump_outputs, dump)
     if c.rank == 0:
         print(json.dumps(out))
     if c.world > 1:

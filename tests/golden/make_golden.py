@@ -23,6 +23,9 @@ text is stored):
                          the documented semantics were seen to differ, over texts of up to 600 bytes with many
                          adjacent candidates; reference(ff=0) outputs.  (The oracle's `match_all_spec` is used
                          only to SELECT inputs; every expectation stored is the real reference's.)
+  differential_vectors.json  test_oracle.py's differential cases (seed 777, the fuzz generator): reference(ff=0)
+                         match count and MatchFull per case, sha256 of the inputs and of all the match lists, so
+                         that the test runs where the reference library is not built.
   highbyte_vectors.json  bytes >= 0x80 in patterns and texts (round 5): signed bracket ranges around 0x7f / 0x80 (the
                          reference compares bytes as signed chars), `.` / \\S / \\D / negated classes over Latin-1 and
                          UTF-8 text, literal windows of high bytes, random patterns over alphabets with high bytes;
@@ -369,6 +372,35 @@ def gen_fuzz(ref: RefProc, count=2500, seed=20260926):
     return out
 
 
+def differential_cases(count=600, seed=777):
+    """The seeded (regex, text) inputs of tests/test_oracle.py::test_live_differential_vs_reference."""
+    rng = random.Random(seed)
+    for _ in range(count):
+        alphabet = rng.choice(ALPHABETS)
+        rx = RegexGen(rng, alphabet).alt(2)
+        text = "".join(rng.choice(alphabet) for _ in range(rng.choice([0, 2, 9, 31, 70])))
+        yield rx, text
+
+
+def gen_differential(ref: RefProc):
+    """The reference's answers to the differential cases, kept small: per case [MatchAll count, MatchFull] (or, where the
+    reference gives no match list, its "crash" / "timeout" / error status: the test passes over those), and the sha256
+    of repr() of the inputs and of all the match lists in order."""
+    cases = list(differential_cases())
+    answers, lists = [], []
+    for rx, text in cases:
+        rxb, txb = rx.encode("latin1"), text.encode("latin1")
+        allm = ref.call("all", rxb, txb, timeout=5.0)
+        if isinstance(allm, list):
+            answers.append([len(allm), ref.call("full", rxb, txb)])
+            lists.append(allm)
+        else:
+            answers.append(allm)
+    print(f"differential: {len(cases)} cases, {len(lists)} with a match list")
+    return dict(inputs_sha256=hashlib.sha256(repr(cases).encode()).hexdigest(), ref=answers,
+                ref_all_sha256=hashlib.sha256(repr(lists).encode()).hexdigest())
+
+
 
 
 # --------------------------------------------------------------------------- bytes >= 0x80
@@ -569,13 +601,15 @@ def dump(name, obj):
 
 def main():
     ref = RefProc()
-    which = sys.argv[1:] or ["testcc", "semantics", "fuzz", "artefact", "highbyte", "bench"]
+    which = sys.argv[1:] or ["testcc", "semantics", "fuzz", "differential", "artefact", "highbyte", "bench"]
     if "testcc" in which:
         dump("testcc_vectors.json", gen_testcc(ref))
     if "semantics" in which:
         dump("semantics_vectors.json", gen_semantics(ref))
     if "fuzz" in which:
         dump("fuzz_vectors.json", gen_fuzz(ref))
+    if "differential" in which:
+        dump("differential_vectors.json", gen_differential(ref))
     if "artefact" in which:
         dump("artefact_vectors.json", gen_artefact(ref))
     if "highbyte" in which:

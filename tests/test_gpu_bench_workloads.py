@@ -11,7 +11,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--fasta-n", "2000000", "--literal-bytes", "200000000",
+SMALL = ["--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline", "--fasta-n", "2000000", "--literal-bytes", "200000000",
          "--tree-files", "300"]
 
 
@@ -35,8 +35,8 @@ def test_two_ranks_equal_one(workload):
     assert two["n_gpus"] == 2 and two["value"] > 0 and two["scaling"] == "weak" and "roofline" in two
     if workload == "regexdna":
         # weak scaling: two ranks hold a 2 x 20 MB text; one rank over the same 40 MB text must count the same
-        one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-extra",
-                              "--no-cpu-baseline", "--fasta-n", "4000000"], capture_output=True, timeout=900, cwd=ROOT)
+        one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
+                              "--no-extra", "--no-cpu-baseline", "--fasta-n", "4000000"], capture_output=True, timeout=900, cwd=ROOT)
         assert one.returncode == 0, one.stderr.decode()[-2000:]
         ref = json.loads([l for l in one.stdout.decode().splitlines() if l.startswith("{")][-1])
         assert two["matches_per_pass"] == ref["matches_per_pass"]

@@ -2,11 +2,10 @@
 
 1. against the expectations written in the reference's own tools/tests/test.cc and the
    outputs of the real reference (use_fast_forward=0) stored in tests/golden/;
-2. live against oracle/_ref/librejit_ref.so on fresh random inputs, when that prebuilt
-   library is present (it always is in the build container).
+2. on a second seed's random inputs, against the real reference's stored answers and, when
+   the prebuilt oracle/_ref/librejit_ref.so is present, against the reference run live.
 """
 import hashlib
-import random
 
 import pytest
 
@@ -127,25 +126,31 @@ def test_regexdna(oracle, nf):
         assert (g["raw_size"], g["stripped_size"], g["replaced_size"]) == (508411, 500000, 668262)
 
 
-@pytest.mark.skipif(not have_ref(), reason="oracle/_ref/librejit_ref.so not built")
 def test_live_differential_vs_reference(oracle):
     """Fresh random patterns every run would not be reproducible; use a second seed than
-    the committed fuzz fixture and compare live.  The generator only emits constructs the
-    reference handles without aborting (see tests/golden/make_golden.py)."""
+    the committed fuzz fixture.  The generator only emits constructs the reference handles
+    without aborting (see tests/golden/make_golden.py).  The reference's answers are stored
+    (tests/golden/differential_vectors.json: per case the match count and MatchFull, a sha256
+    of all the match lists); when oracle/_ref is built the reference also runs live."""
     import sys, os
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    from make_golden import RegexGen, ALPHABETS, RefProc
-    ref = RefProc()
-    rng = random.Random(777)
-    checked = 0
-    for _ in range(600):
-        alphabet = rng.choice(ALPHABETS)
-        rx = RegexGen(rng, alphabet).alt(2).encode("latin1")
-        text = "".join(rng.choice(alphabet) for _ in range(rng.choice([0, 2, 9, 31, 70]))).encode("latin1")
-        r = ref.call("all", rx, text, timeout=5.0)
-        if not isinstance(r, list):
+    from make_golden import differential_cases, RefProc
+    g = V.differential()
+    cases = list(differential_cases())
+    assert hashlib.sha256(repr(cases).encode()).hexdigest() == g["inputs_sha256"]   # the generator still makes the recorded inputs
+    ref = RefProc() if have_ref() else None
+    lists = []
+    for (rx, text), want in zip(cases, g["ref"]):
+        rx, text = V.b(rx), V.b(text)
+        r = ref.call("all", rx, text, timeout=5.0) if ref is not None else None
+        if not isinstance(want, list):
+            assert ref is None or r == want, (rx, text)
             continue
-        assert oracle.match_all(rx, text) == r, (rx, text)
-        assert oracle.match_full(rx, text) == ref.call("full", rx, text), (rx, text)
-        checked += 1
-    assert checked > 500
+        allm = oracle.match_all(rx, text)
+        if ref is not None:
+            assert allm == r, (rx, text)
+            assert oracle.match_full(rx, text) == ref.call("full", rx, text), (rx, text)
+        assert isinstance(allm, list) and [len(allm), oracle.match_full(rx, text)] == want, (rx, text)
+        lists.append(allm)
+    assert hashlib.sha256(repr(lists).encode()).hexdigest() == g["ref_all_sha256"]
+    assert len(lists) > 500

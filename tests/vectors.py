@@ -40,6 +40,10 @@ def artefact():
     return _load("artefact_vectors.json")
 
 
+def differential():
+    return _load("differential_vectors.json")
+
+
 def highbyte():
     return _load("highbyte_vectors.json")
 

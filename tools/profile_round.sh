@@ -8,12 +8,12 @@ out=$root/gpurun_out; mkdir -p $out
 make -C $root/samples > /dev/null 2>&1
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_kt /tmp/prof_full /tmp/prof_f /tmp/prof_w /tmp/prof_sq /tmp/prof_lin
-python $root/bench.py > $out/prof_${tag}_bench.json 2> /tmp/b.log
+python $root/bench.py --full > $out/prof_${tag}_bench.json 2> $TMPDIR/b.log
 # headline run only (no extras, no CPU sample): the per-kernel averages then are those of the timed region
 rocprofv3 --kernel-trace --stats -d /tmp/prof_kt -o r -- python $root/bench.py --no-extra --no-cpu-baseline > $out/prof_${tag}_bench_profiled.json 2> /tmp/kt.log
 python $root/tools/rocpd_stats.py $(find /tmp/prof_kt -name "*.db" | head -1) 12 > $out/prof_${tag}_kernel_stats.txt
 # every extra of the bench line, the 50 GB literal scan and the 2.5 GB runs included: one table
-rocprofv3 --kernel-trace --stats -d /tmp/prof_full -o r -- python $root/bench.py --no-cpu-baseline --steps 5 --jrep-files 5000 --jrep-bytes 500000000 > /dev/null 2> /tmp/full.log
+rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_full -o r -- python $root/bench.py --full --no-cpu-baseline --steps 5 --jrep-files 5000 --jrep-bytes 500000000 > /dev/null 2> $TMPDIR/full.log
 python $root/tools/rocpd_stats.py $(find /tmp/prof_full -name "*.db" | head -1) 56 split > $out/prof_${tag}_kernel_stats_full.txt
 # the linear-time carry scan and the dense / class patterns, first and warm calls
 rocprofv3 --kernel-trace --stats -d /tmp/prof_lin -o r -- python $root/tools/linear_probe.py > $out/prof_${tag}_linear_probe.txt 2> /tmp/lin.log
@@ -23,12 +23,12 @@ rm -rf /tmp/prof_linf
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/prof_linf -o r -- python $root/tools/linear_probe.py "[acgt]+" "a.*b" > /dev/null 2> /tmp/linf.log
 python $root/tools/pmc_summary.py /tmp/prof_linf FETCH_SIZE > $out/prof_${tag}_pmc_fetch_linear.txt
 # PMC passes: one counter group per run (the big runs included: no more `traffic: null`)
-PMC_CMD="python $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline --jrep-files 2000 --jrep-bytes 200000000"
+PMC_CMD="python $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --jrep-files 2000 --jrep-bytes 200000000"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/prof_f -o r -- $PMC_CMD > /dev/null 2> /tmp/f.log
 python $root/tools/pmc_summary.py /tmp/prof_f FETCH_SIZE > $out/prof_${tag}_pmc_fetch.txt
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/prof_w -o r -- $PMC_CMD > /dev/null 2> /tmp/w.log
 python $root/tools/pmc_summary.py /tmp/prof_w WRITE_SIZE > $out/prof_${tag}_pmc_write.txt
-rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d /tmp/prof_sq -o r -- python $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-big > /dev/null 2> /tmp/sq.log
+rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $TMPDIR/prof_sq -o r -- python $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-big > /dev/null 2> $TMPDIR/sq.log
 for c in SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY; do
   echo "## $c"; python $root/tools/pmc_summary.py /tmp/prof_sq $c | head -16
 done > $out/prof_${tag}_pmc_sq.txt
