@@ -54,7 +54,18 @@ typedef struct {
                               * section 6).  A RANGE of such a pattern (rj_scan_run with own_begin / own_end) owns the whole
                               * segments between synchronisation points, [first point >= own_begin, first point >= own_end),
                               * and takes the text buffer to be the WHOLE text: give every rank the text up to its end
-                              * (rejit_amd/sharding.py: visible_range(..., whole_text=True)), not a fixed halo. */
+                              * (rejit_amd/sharding.py: visible_range(..., whole_text=True)), not a fixed halo.
+                              * Where the artefact can apply (a candidate begins where another ends) and no exact replay can
+                              * take the call, the call fails with RJ_TOO_LARGE and rj_last_error() names the ring artefact and
+                              * the limit: the answer is the reference's or none, never the documented semantics in its place.
+                              * The limits are budgets of one-lane work (rejit_amd/csrc/engine_internal.h): about 2.4 s for
+                              * automata of more than 1024 positions (one lane over the whole text), about 2 s for rings of more
+                              * than 448 slots (one lane per stretch without a synchronisation point), and up to about 15 s for a
+                              * long stretch whose parts the parallel replay could not take (more order patterns at its cuts than
+                              * rounds, snapshots that do not fit), which is then replayed on one lane; beyond, and for a stretch
+                              * of more than 1 GiB or a grown batch whose scratch does not fit, RJ_TOO_LARGE.  An own range that
+                              * the replay cannot serve is answered from the text's beginning (the run covers the starts before
+                              * own_end) when no candidate there begins where another ends. */
   int32_t reserved;
 } rj_info;
 

@@ -676,7 +676,6 @@ static int run_pairs(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb,
   return 1;
 }
 
-constexpr uint64_t kExactLimit = 1u << 20;  // bytes the one-lane exact kernel is allowed to walk
 constexpr uint64_t kDenseSegment = 1ull << 27;  // dense mode: starts per pipeline run (bounds the lists)
 
 // One full pipeline over the starts [sb, se): scan -> region offsets -> verify -> finalize.
@@ -827,8 +826,9 @@ static int run_range(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb,
     fp.have_prev = have_prev;
     // bit-exactness with the reference's ring artefact (Q8) can only be at stake when the
     // pattern is at risk AND a candidate begins exactly where another one ends
-    const bool whole_text = sb == 0 && se == n + 1 && carry_cur == 0 && !have_prev;
-    fp.detect_adjacent = rp->host->q8_risk && whole_text;
+    // (from the text's beginning: the range [0, se) of a pattern too wide for the exact replay included -- run_pipeline)
+    const bool from_start = sb == 0 && carry_cur == 0 && !have_prev;
+    fp.detect_adjacent = rp->host->q8_risk && from_start;
     fp.detect_conflict = behind;
     fp.expand = expand;
     VerifyParams vp{};
@@ -1018,7 +1018,7 @@ static int run_range(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb,
 }
 
 // automata too wide for the exact replay's synchronisation scan: the reference's loop on ONE lane over the
-// whole text, up to kExactLimit bytes
+// whole text, up to kSequentialBudget units of work (engine_internal.h)
 static int run_exact_one_lane(rj_scan* s, const uint8_t* d_text, uint64_t n, hipStream_t st) {
   const rj_program* rp = s->prog;
   RJ_HIP(s->ring.reserve(static_cast<size_t>(rp->graph.times) * rp->graph.n_states * sizeof(int64_t)));
@@ -1034,6 +1034,41 @@ static int run_exact_one_lane(rj_scan* s, const uint8_t* d_text, uint64_t n, hip
   return RJ_OK;
 }
 
+// A call that needs the reference's answer (a pattern at risk of its ring artefact, on a text where the artefact can apply)
+// and that no replay could give: RJ_TOO_LARGE -- the documented semantics would differ from the reference's answer.
+static int refuse_exact(rj_scan* s) {
+  s->result = nullptr;
+  s->result_count = 0;
+  return fail(RJ_TOO_LARGE, "ring artefact: the reference's answer needs the exact replay, which cannot take this call (%s)",
+              s->exact_limit ? s->exact_limit : "no replay for this pattern");
+}
+
+// s->result (ordered by begin) cut to the matches that begin in [lo, hi)
+static int keep_begins(rj_scan* s, uint64_t lo, uint64_t hi, hipStream_t st) {
+  if (s->result_count == 0) return RJ_OK;
+  auto first_at_or_after = [&](uint64_t x, uint64_t* at) -> int {
+    uint64_t a = 0, b = s->result_count;   // the first index whose begin is >= x lies in [a, b]
+    while (a < b) {
+      const uint64_t m = a + (b - a) / 2;
+      uint64_t begin = 0;
+      RJ_HIP(hipMemcpyAsync(&begin, s->result + 2 * m, sizeof(begin), hipMemcpyDefault, st));
+      RJ_HIP(hipStreamSynchronize(st));
+      if (begin >= x) b = m;
+      else a = m + 1;
+    }
+    *at = a;
+    return RJ_OK;
+  };
+  uint64_t i = 0, j = 0;
+  int rc = first_at_or_after(lo, &i);
+  if (rc != RJ_OK) return rc;
+  rc = first_at_or_after(hi, &j);
+  if (rc != RJ_OK) return rc;
+  s->result += 2 * i;
+  s->result_count = j - i;
+  return RJ_OK;
+}
+
 int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, uint64_t carry_cur,
                  uint64_t carry_prev_end, int have_prev, hipStream_t st) {
   const rj_program* rp = s->prog;
@@ -1046,6 +1081,7 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
   if ((reinterpret_cast<uintptr_t>(d_text) & 15u) != 0) return fail(RJ_BAD_ARGUMENT, "device text must be 16-byte aligned");
   const auto wall0 = std::chrono::steady_clock::now();
   const bool whole_text = sb == 0 && se == n + 1 && carry_cur == 0 && !have_prev;
+  uint64_t keep_from = sb;
   if (rp->host->q8_risk && !whole_text && exact_replay_fits(rp)) {
     // A pattern at risk of the reference's ring artefact (Q8) over a RANGE of the text: the artefact's
     // state crosses any cut that is not a synchronisation point of the reference's loop, so the range owns
@@ -1060,8 +1096,24 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
       s->stats.n_matches = s->result_count;
       return RJ_OK;
     }
-    // (a stretch too long to replay: the documented semantics, as for any other pattern)
+    // (a stretch the replay cannot take: the range still owns the segments between the same points, answered below)
+    if (!s->xr_ends_known) return refuse_exact(s);
+    keep_from = s->xr_y0;
+    se = s->xr_y1;
   }
+  // An own range of an at-risk pattern that the replay did not serve owns the matches that BEGIN in [keep_from, se) -- [sb, se)
+  // for automata too wide for the replay (more than 1024 positions: no synchronisation points), the replay's own segments
+  // otherwise -- taken from the whole text's answer, which the greedy selection decides from the candidates that begin before
+  // se.  So the run covers the starts [0, se) from the text's beginning (no carry: a range of an at-risk pattern has none) with
+  // the adjacency check on, takes the reference's answer below when the artefact can apply (or refuses the call), and keeps the
+  // matches that begin at or after keep_from.
+  const bool cut_range = rp->host->q8_risk && !whole_text;
+  if (cut_range) {
+    if (keep_from >= se) return RJ_OK;
+    sb = carry_cur = carry_prev_end = 0;
+    have_prev = 0;
+  }
+  const bool from_start = sb == 0 && carry_cur == 0 && !have_prev;
   static const bool no_small = getenv("RJ_NO_SMALL") != nullptr;  // measurement override
   if (n <= kSmallMaxText && rp->dev.n_words <= 4 && rp->dev.table_words <= kSmallMaxTableWords && !no_small &&
       small_lds_bytes(rp->dev, static_cast<uint32_t>(n)) <= small_lds_limit()) {
@@ -1093,6 +1145,10 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
     if (s->small_hdr[1] == 0) {
       s->result_count = s->small_hdr[0];
       s->result = s->small_out;   // pinned host memory: readable from the device and from the host
+      if (cut_range) {
+        int rc = keep_begins(s, keep_from, se, st);
+        if (rc != RJ_OK) return rc;
+      }
       s->stats.n_candidates = s->result_count;
       s->stats.n_matches = s->result_count;
       s->stats.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
@@ -1137,15 +1193,25 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
     s->result_count = total;
     s->result = s->acc_out.as<uint64_t>();
   }
-  if (rp->host->q8_risk && whole_text && (s->want_exact || s->stats.linear_path || !single_run)) {
+  if (rp->host->q8_risk && from_start && (s->want_exact || s->stats.linear_path || !single_run)) {
     // the result may differ from the reference's by the ring artefact (a candidate begins exactly where
     // another ends; the carry scan and the segmented dense runs do not look for that): take the
-    // reference's own answer
+    // reference's own answer, or refuse the call when no replay can give it
     int rc = 0;
-    if (exact_replay_fits(rp)) rc = run_exact(s, d_text, n, 0, n + 1, st);
-    else if (n <= kExactLimit && rp->graph.n_states > 0) rc = run_exact_one_lane(s, d_text, n, st) == RJ_OK ? 1 : RJ_DEVICE_ERROR;
+    s->exact_limit = nullptr;
+    if (exact_replay_fits(rp)) {
+      rc = run_exact(s, d_text, n, 0, n + 1, st);   // (whole text: the replay's own ranges returned above)
+    } else if (rp->graph.n_states > 0) {
+      if (n <= kSequentialBudget / one_lane_work(rp->graph)) rc = run_exact_one_lane(s, d_text, n, st) == RJ_OK ? 1 : RJ_DEVICE_ERROR;
+      else s->exact_limit = "more than 1024 automaton positions: one lane over the whole text, more work than a call's budget";
+    }
     if (rc < 0) return rc;
-    if (rc == 1) s->stats.exact_path = s->xr_parts != 0 ? 2 : 1;
+    if (rc == 0) return refuse_exact(s);
+    s->stats.exact_path = s->xr_parts != 0 ? 2 : 1;
+  }
+  if (cut_range) {
+    int rc = keep_begins(s, keep_from, se, st);
+    if (rc != RJ_OK) return rc;
   }
   // (every run_range ends with a stream synchronise, so the host clock covers the whole pipeline
   // and no event commands are needed on the stream)

@@ -109,6 +109,9 @@ struct rj_scan {
   rejit_amd::DeviceBuffer xr_snaps, xr_raw_n, xr_fix_ring;  // long segments taken in parts (speculate and verify)
   uint64_t xr_parts = 0, xr_rounds = 0;                     // of the last exact replay: parts of long segments, rounds beyond the first
   bool want_exact = false;         // the run just made may differ from the reference by the ring artefact (Q8)
+  const char* exact_limit = nullptr;  // why the last exact replay gave up (run_exact returned 0): the limit it hit
+  bool xr_ends_known = false;         // ... and the ends of the range it owned, [first point >= sb, first point >= se), when it found them
+  uint64_t xr_y0 = 0, xr_y1 = 0;
   rejit_amd::DeviceBuffer with_buf, long_gaps, repl_out;  // replace_gather
   uint64_t repl_len = 0;           // rj_replace_all_begin: the new text waits in repl_out for rj_replace_all_fetch
   bool repl_valid = false;
@@ -194,6 +197,27 @@ int run_linear(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint6
 // too wide, or a stretch without synchronisation point too long to replay), < 0 = error.
 bool exact_replay_fits(const rj_program* rp);
 int run_exact(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, hipStream_t st);
+
+// ONE lane walking the reference's loop -- exact_sequential over a whole text (automata of more than 1024 positions), xr_replay
+// over one stretch between synchronisation points (rings of more than 448 slots) -- costs per text byte about
+//     work = times x n_states  +  64 x byte edges  +  2 x control edges^2
+// units (the ring's slots; every byte edge a dependent global load; the control edges relaxed to a fixed point).  Measured on
+// the MI355X, 4 and 16 KiB, the difference of the two: exact_sequential 44.9 us per byte at work 9140 (`.{0,2}(w1|..|w140)`,
+// 44 slots, 142 byte edges) and 8.8 us at 1676 (`[ab]{0,2}(L1|..|L20)`, 64-byte literals, 260 slots): ~5 ns per unit;
+// xr_replay 11.2 us at 1546 (`.{0,8}(L1|..|L4)`, 650 slots) and 24.6 us at 3766 (`.{0,20}(...)`, 1430 slots), and the
+// 185 us per byte on record for a pattern of 102 control edges at 25003: ~7 ns per unit.  A call walks at most a budget of units
+// (bytes x work) on one lane -- about 2.4 s of exact_sequential, 2 s of xr_replay; beyond, the exact answer is refused
+// (RJ_TOO_LARGE), never guessed.  (The sequential budget still takes test_gpu_linear.py's `(w1|...|w900)+` over 7 KB: 4.1e8.)
+constexpr uint64_t kSequentialBudget = 7ull << 26;   // exact_sequential: 4.7e8 units
+constexpr uint64_t kReplayLaneBudget = 1ull << 28;   // xr_replay, one lane per stretch: 2.7e8 units
+// (a stretch the parts could not take -- more order patterns at the cuts than rounds -- was replayed on one lane until round 4
+// and is again, within 8 times that: up to ~15 s by the estimate, which overstates rings in LDS; tests/test_gpu_mid.py's
+// random patterns over 300 KB need up to 1.5e9 units)
+constexpr uint64_t kPartsFallbackBudget = 8 * kReplayLaneBudget;
+inline uint64_t one_lane_work(const DevGraph& G) {
+  const uint64_t ce = static_cast<uint64_t>(G.n_control_edges);
+  return static_cast<uint64_t>(G.times) * G.n_states + 64 * static_cast<uint64_t>(G.n_byte_edges) + 2 * ce * ce;
+}
 
 // multi_device.hip: one call over every visible device (false = not applicable, take the one-device path)
 bool multi_device_match_all(const rj_program* prog, const char* text, size_t n, uint64_t** spans, int64_t* result);

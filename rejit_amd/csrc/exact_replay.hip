@@ -28,8 +28,9 @@
 //   xr_join        one lane over the PARTS: a part pops from the lists before it while begin >= its smallest raw begin, and
 //                  drops its first entry when the sink's filter says so; the parts' lists then go to xr_compact as they are
 // and xr_offsets / xr_compact carry on as for the other segments.  What remains: a segment must fit a batch (which grows
-// from 64 MiB to 1 GiB when it has to), the cuts must not meet more than kReplayMaxRounds different order patterns, and rings of more than kWalkSlots slots keep the one-lane replay (<= 16 MiB): otherwise run_exact
-// reports "not done" and the caller keeps the result of the parallel pipeline (documented semantics).
+// from 64 MiB to 1 GiB when it has to), the cuts must not meet more than kReplayMaxRounds different order patterns, and rings of more than kWalkSlots slots keep the one-lane replay (at most kReplayLaneBudget units of work per call,
+// engine_internal.h): otherwise run_exact reports "not done" (s->exact_limit names the limit) and the caller refuses the call with
+// RJ_TOO_LARGE wherever the reference's answer is needed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,7 +46,6 @@ namespace {
 constexpr uint64_t kChunk = 1024;
 constexpr uint64_t kBatchChunks = 65536;        // 64 MiB of text per batch ...
 constexpr uint64_t kBigBatchChunks = 1u << 20;  // ... and up to 1 GiB (16 GiB of scratch) when a batch holds no second synchronisation point
-constexpr uint64_t kMaxSegment = 16ull << 20;   // longest stretch ONE lane is asked to replay (rings too large for the walk)
 constexpr uint64_t kLongSegment = 64ull << 10;  // a longer segment is taken in parts
 constexpr uint64_t kPart = 2048, kWarm = 512;   // bytes per part; bytes before a part its replay starts at
 constexpr int kWalkSlots = 448;                 // times x states up to this: xr_walk holds the true ring, its pattern and the candidates in LDS (16 x 448 x 8 B)
@@ -398,12 +398,20 @@ int run_exact_nq(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
     rc = first_point(se, &y1);
     if (rc != RJ_OK) return rc;
   }
+  s->xr_ends_known = true;
+  s->xr_y0 = y0;
+  s->xr_y1 = y1;
   const int slots = G.n_states * G.times;
   const bool lds = slots <= kLdsRingSlots;
   // (the pairs go to a buffer of their own: when a later batch turns out not to be replayable the caller
   // keeps the result it has)
   uint64_t batch_chunks = kBatchChunks;
+  const uint64_t lane_work = one_lane_work(G);
+  // (long stretches whose parts cannot be replayed -- more order patterns at the cuts than rounds, snapshots that do not fit --
+  // are replayed again on one lane each, as rings too wide for the walk are, when that fits a call's budget)
+  bool one_lane = false;
   for (int attempt = 0; attempt < 8; attempt++) {
+    uint64_t lane_cost = 0;   // (rings too wide for the walk: the one-lane work of the batches so far, the longest stretch of each)
     if (y0 >= y1) {  // nothing begins in this range
       s->result_count = 0;
       s->result = s->out.as<uint64_t>();
@@ -424,12 +432,15 @@ int run_exact_nq(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
     RJ_HIP(s->xr_counts.reserve(cap_chunks * sizeof(uint32_t)));
     if (s->xr_scratch.reserve((cap_chunks * kChunk + 1) * 2 * sizeof(uint64_t)) != hipSuccess) {
       (void)hipGetLastError();
-      if (batch_chunks > kBatchChunks) return 0;  // (a grown batch: 16 bytes of scratch per text byte did not fit -- not replayed)
+      if (batch_chunks > kBatchChunks) {  // (a grown batch: 16 bytes of scratch per text byte did not fit -- not replayed)
+        s->exact_limit = "the scratch of a grown batch (a stretch of more than 64 MiB without a synchronisation point) did not fit";
+        return 0;
+      }
       return rj_fail(RJ_DEVICE_ERROR, "exact replay: out of device memory");
     }
     const int replay_blocks = static_cast<int>(std::min<uint64_t>((cap_chunks + kReplayLanes - 1) / kReplayLanes, 2048));
     if (!lds) RJ_HIP(s->ring.reserve(static_cast<size_t>(replay_blocks) * kReplayLanes * slots * sizeof(int64_t)));
-    bool grow_batch = false;
+    bool grow_batch = false, retry_one_lane = false;
     for (uint64_t ys = y0; ys < y1;) {
       const uint64_t nb = std::min((y1 - ys + kChunk - 1) / kChunk, batch_chunks);
       const int final = ys + nb * kChunk >= y1 ? 1 : 0;
@@ -446,13 +457,24 @@ int run_exact_nq(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
       const bool can_walk = slots <= kWalkSlots;
       if (!final && last == ys) {
         // (larger batches, from the beginning: the parts make a segment of a gigabyte a matter of seconds)
-        if (!can_walk || batch_chunks >= kBigBatchChunks) return 0;
+        if (!can_walk || batch_chunks >= kBigBatchChunks) {
+          s->exact_limit = !can_walk ? "a stretch without a synchronisation point longer than a batch, with a ring of more than 448 slots"
+                                     : "a stretch of more than 1 GiB without a synchronisation point";
+          return 0;
+        }
         batch_chunks *= 4;
         grow_batch = true;
         break;
       }
-      if (!can_walk && h[kXrMaxGap] > kMaxSegment) return 0;  // (one lane would take minutes)
-      const bool has_long = can_walk && h[kXrMaxGap] > kLongSegment;
+      if (!can_walk || one_lane) {  // (one lane per stretch: the longest decides the batch's time)
+        lane_cost += h[kXrMaxGap] * lane_work;
+        if (lane_cost > (one_lane && can_walk ? kPartsFallbackBudget : kReplayLaneBudget)) {
+          s->exact_limit = one_lane ? "a long stretch whose parts the replay could not take, more one-lane work than a call's budget"
+                                    : "a ring of more than 448 slots over stretches without a synchronisation point: more one-lane work than a call's budget";
+          return 0;
+        }
+      }
+      const bool has_long = can_walk && !one_lane && h[kXrMaxGap] > kLongSegment;
       const uint64_t max_len = has_long ? kLongSegment : ~0ull;
       const int rb = static_cast<int>(std::min<uint64_t>((nb + kReplayLanes - 1) / kReplayLanes, static_cast<uint64_t>(replay_blocks)));
       if (lds)
@@ -488,7 +510,8 @@ int run_exact_nq(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
           if (s->xr_snaps.reserve((static_cast<size_t>(kReplayMaxRounds) + 3 + (static_cast<size_t>(kReplayMaxRounds) + 3) * n_parts + 2 * lanes) * ring_bytes) != hipSuccess ||
               s->xr_raw_n.reserve(n_parts * 2 * sizeof(uint32_t)) != hipSuccess) {
             (void)hipGetLastError();
-            return 0;
+            retry_one_lane = true;   // (the snapshots of the parts do not fit in device memory)
+            break;
           }
           int64_t* cands = s->xr_snaps.as<int64_t>();
           int64_t* walk_ring = cands + static_cast<size_t>(kReplayMaxRounds + 1) * slots;
@@ -518,7 +541,10 @@ int run_exact_nq(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
             RJ_HIP(hipMemcpyAsync(h, state, sizeof(h), hipMemcpyDeviceToHost, st));
             RJ_HIP(hipStreamSynchronize(st));
             if (h[kXrWalkStuck] == 0) break;
-            if (n_cand > kReplayMaxRounds) return 0;  // (more order patterns at the cuts than rounds: given up)
+            if (n_cand > kReplayMaxRounds) {  // (more order patterns at the cuts than rounds: the parts are given up)
+              retry_one_lane = true;
+              break;
+            }
             // the pattern that stopped the walk becomes candidate n_cand: every part from there on is replayed from it
             RJ_HIP(hipMemcpyAsync(cands + static_cast<size_t>(n_cand) * slots, walk_pat, ring_bytes, hipMemcpyDeviceToDevice, st));
             cand_from.v[n_cand] = h[kXrWalkNext];
@@ -526,6 +552,7 @@ int run_exact_nq(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
             n_cand++;
             s->xr_rounds++;
           }
+          if (retry_one_lane) break;
           uint64_t* min_begin = reinterpret_cast<uint64_t*>(exits);  // (the exit rings are done with: at least 3 n_parts words)
           if (lds)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(xr_emit<true>), dim3(blocks), dim3(kReplayLanes), lds_bytes, st, G, d_text, n, a, b, ys, n_parts, chosen,
@@ -540,6 +567,7 @@ int run_exact_nq(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
                              s->xr_sync.as<uint64_t>(), s->xr_counts.as<uint32_t>());
           s->xr_parts += n_parts;
         }
+        if (retry_one_lane) break;
       }
       hipLaunchKernelGGL(xr_offsets, dim3(1), dim3(1024), 0, st, s->xr_counts.as<uint32_t>(), nb, s->xr_offs.as<uint64_t>(), state);
       hipLaunchKernelGGL(xr_compact, dim3(static_cast<int>((nb * 64 + 255) / 256)), dim3(256), 0, st, s->xr_sync.as<uint64_t>(),
@@ -547,7 +575,8 @@ int run_exact_nq(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
                          s->xr_out.as<uint64_t>(), s->xr_out_cap);
       ys = final ? y1 : last;
     }
-    if (grow_batch) continue;
+    if (retry_one_lane) one_lane = true;
+    if (grow_batch || retry_one_lane) continue;
     RJ_HIP(hipMemcpyAsync(h, state, sizeof(h), hipMemcpyDeviceToHost, st));
     RJ_HIP(hipStreamSynchronize(st));
     RJ_HIP(hipGetLastError());
@@ -571,7 +600,12 @@ bool exact_replay_fits(const rj_program* rp) { return rp->host->q8_risk && rp->d
 
 int run_exact(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, hipStream_t st) {
   const rj_program* rp = s->prog;
-  if (!exact_replay_fits(rp)) return 0;
+  s->exact_limit = nullptr;
+  s->xr_ends_known = false;
+  if (!exact_replay_fits(rp)) {
+    s->exact_limit = "more than 1024 automaton positions";
+    return 0;
+  }
   if (se > n + 1) se = n + 1;
   if (rp->dev.n_words <= 2) return run_exact_nq<1>(s, d_text, n, sb, se, st);
   if (rp->dev.n_words <= 4) return run_exact_nq<2>(s, d_text, n, sb, se, st);

@@ -1283,7 +1283,9 @@ void launch_match_small(const SmallParams& a, const DevProgram& P, hipStream_t s
 // MatchAllAppendFilter, src/codegen.cc:36-86).  It exists for bit-exactness only: it reproduces
 // the ring-slot artefact "Q8"  that the parallel pipeline -- which
 // implements the documented semantics -- does not, and runs only when a pattern can hit that
-// artefact AND two candidates are adjacent.  Sequential by nature: ~1 us per text byte.
+// artefact AND two candidates are adjacent.  Sequential by nature: measured on the MI355X 8.8 us per text byte
+// (`[ab]{0,2}(L1|..|L20)`, 64-byte literals) to 45 us (`.{0,2}(w1|..|w140)`: every byte edge is a dependent global
+// load), ~5 ns per unit of one_lane_work (engine_internal.h); run_pipeline keeps a call within kSequentialBudget.
 __global__ void exact_sequential(const uint8_t* t, uint64_t n, DevGraph G, int64_t* ring, uint64_t* out,
                                  uint64_t out_cap, unsigned long long* counters) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;

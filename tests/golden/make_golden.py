@@ -30,6 +30,10 @@ text is stored):
                          reference compares bytes as signed chars), `.` / \\S / \\D / negated classes over Latin-1 and
                          UTF-8 text, literal windows of high bytes, random patterns over alphabets with high bytes;
                          texts of up to 5000 bytes; reference(ff=0) outputs.
+  wide_artefact_vectors.json  at-risk patterns past the exact replay's limits (tests/wide_artefact_cases.py: rings of more
+                         than 448 slots, automata of more than 1024 positions, and a control class within them) over seeded
+                         texts of 1, 16 and 64 KiB: reference(ff=0) MatchAll count, MatchFull, MatchFirst, sha256 of the span
+                         list; whether the documented semantics differ.
   bench_vectors.json     the 12 benchmark regexps (tools/benchmarks/run.py:347-360) on
                          seeded random text with planted matches; regexdna patterns on the
                          FASTA n=50000 input; reference(ff=0) outputs (offsets or digest).
@@ -519,6 +523,33 @@ def gen_artefact(ref: RefProc, seed=20260927):
     print(f"artefact: {len(out)} vectors over {len(pats)} patterns; the reference differs from the documented semantics on {differ}")
     return out
 
+# --------------------------------------------------------------------------- the ring artefact past the replay's limits
+def gen_wide_artefact(ref: RefProc):
+    """wide_artefact_cases.py's patterns (classes A, B, C) over their seeded texts: per case the reference's MatchAll count,
+    MatchFull, MatchFirst, the first span of its MatchAll and the sha256 of its span list (digest()), the text's sha256 (the generator is checked, not trusted),
+    and whether the documented semantics (the oracle's match_all_spec) differ from the reference's answer."""
+    import wide_artefact_cases as WA
+    from checkers import Oracle
+    oracle = Oracle()
+    cases, differ = [], 0
+    for c in WA.patterns():
+        rxb = c["regex"].encode()
+        for size in WA.SIZES:
+            for kind in WA.KINDS:
+                text = WA.make_text(c, size, kind)
+                allm = ref.call("all", rxb, text, timeout=60.0)
+                full = ref.call("full", rxb, text, timeout=60.0)
+                first = ref.call("first", rxb, text, timeout=60.0)
+                assert isinstance(allm, list) and full in (0, 1) and (first is None or isinstance(first, tuple)), (c["name"], size, kind)
+                d = [tuple(x) for x in oracle.match_all_spec(rxb, text)] != [tuple(x) for x in allm]
+                differ += d
+                cases.append(dict(name=c["name"], size=size, kind=kind, text_sha256=hashlib.sha256(text).hexdigest(), count=len(allm),
+                                  full=full, first=list(first) if first else None, all_first=list(allm[0]) if allm else None,
+                                  spans_sha256=digest(allm), spec_differs=d))
+    print(f"wide artefact: {len(cases)} cases, the documented semantics differ on {differ}")
+    return dict(seed=WA.SEED, patterns=[dict(name=c["name"], cls=c["cls"], regex=c["regex"]) for c in WA.patterns()], cases=cases)
+
+
 # --------------------------------------------------------------------------- bench-shaped
 def digest(ms):
     h = hashlib.sha256()
@@ -601,7 +632,7 @@ def dump(name, obj):
 
 def main():
     ref = RefProc()
-    which = sys.argv[1:] or ["testcc", "semantics", "fuzz", "differential", "artefact", "highbyte", "bench"]
+    which = sys.argv[1:] or ["testcc", "semantics", "fuzz", "differential", "artefact", "highbyte", "bench", "wide_artefact"]
     if "testcc" in which:
         dump("testcc_vectors.json", gen_testcc(ref))
     if "semantics" in which:
@@ -616,6 +647,8 @@ def main():
         dump("highbyte_vectors.json", gen_highbyte(ref))
     if "bench" in which:
         dump("bench_vectors.json", gen_bench(ref))
+    if "wide_artefact" in which:
+        dump("wide_artefact_vectors.json", gen_wide_artefact(ref))
 
 
 if __name__ == "__main__":

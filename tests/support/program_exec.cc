@@ -373,6 +373,25 @@ int pe_plan(const char* re, uint64_t* info, uint32_t* window_values) {
 }
 
 
+// the exact replay's view of a pattern (exact_replay.hip): info[0] positions, [1] n_words (the synchronisation-point walk takes
+// up to 32), [2] the ring's times x n_states slots (the parallel replay's walk takes up to 448), [3] times, [4] n_states, [5] q8_risk,
+// [6] byte edges, [7] control edges
+int pe_ring_info(const char* re, uint64_t* info) {
+  LowerResult lr = lower(re);
+  if (lr.status != 0) return lr.status;
+  const Program& P = *lr.program;
+  const GraphBlob b = make_graph_blob(P.graph);
+  info[0] = (uint64_t)P.n_pos;
+  info[1] = (uint64_t)P.n_words;
+  info[2] = (uint64_t)b.times * (uint64_t)b.n_states;
+  info[3] = (uint64_t)b.times;
+  info[4] = (uint64_t)b.n_states;
+  info[5] = P.q8_risk ? 1 : 0;
+  info[6] = (uint64_t)b.n_byte_edges;
+  info[7] = (uint64_t)b.n_control_edges;
+  return 0;
+}
+
 // exact_count.h: the plan of MatchAllCount-in-one-kernel for `n_rx` patterns and `n_bases` base windows (8 bytes each).
 // 1 = the set has the shape (table_out: kExactTabWords words, base_out: lo[2], hi[2]), 0 = refused, < 0 = a pattern
 // does not compile.
