@@ -29,12 +29,12 @@
 #include "device_program.h"
 #include "kernels.h"
 #include "tile_lookback.h"
+#include "wave_ops.h"
 
 namespace rejit_amd {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr uint64_t kIter = 2048;                    // bytes per wave iteration: 64 lanes x 32
 constexpr int kTileIters = 16;
 constexpr uint64_t kTile = kIter * kTileIters;      // 32 KiB: a wave's tile (four of them are a unit of the prefix scan)
@@ -45,24 +45,6 @@ constexpr int kTilesPerTicket = 4;
 #define RJ_DS_AHEAD 1
 #endif
 constexpr int kAhead = RJ_DS_AHEAD;                 // iterations of text in flight per wave (2: two buffers, each reloaded behind its class streams)
-
-__device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t x) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROW_MASK, 0xF, true));
-}
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
-  x += dpp_or_zero<0x111, 0xF>(x);
-  x += dpp_or_zero<0x112, 0xF>(x);
-  x += dpp_or_zero<0x114, 0xF>(x);
-  x += dpp_or_zero<0x118, 0xF>(x);
-  x += dpp_or_zero<0x142, 0xA>(x);
-  x += dpp_or_zero<0x143, 0xC>(x);
-  return x;
-}
-__device__ __forceinline__ uint32_t wave_from_lane_below(uint32_t x) { return dpp_or_zero<0x138, 0xF>(x); }  // wave_shr:1, lane 0 gets 0
-__device__ __forceinline__ uint32_t wave_last_lane(uint32_t x) { return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), kWave - 1)); }
 
 struct AnyLane {
   __device__ __forceinline__ bool operator()(uint32_t x) const { return __ballot(x != 0) != 0; }

@@ -27,34 +27,16 @@
 #include "device_program.h"
 #include "kernels.h"
 #include "tile_lookback.h"
+#include "wave_ops.h"
 
 namespace rejit_amd {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr uint64_t kChunk = 1024;
 constexpr int kTileChunks = 32;                        // chunks per tile (four tiles, one per wave, are a unit of the prefix scan)
 constexpr uint64_t kTile = kChunk * kTileChunks;       // 32 KiB
 constexpr int kDepth = 8;                              // chunk loads in flight per wave
-
-__device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t x) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROW_MASK, 0xF, true));
-}
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
-  x += dpp_or_zero<0x111, 0xF>(x);
-  x += dpp_or_zero<0x112, 0xF>(x);
-  x += dpp_or_zero<0x114, 0xF>(x);
-  x += dpp_or_zero<0x118, 0xF>(x);
-  x += dpp_or_zero<0x142, 0xA>(x);
-  x += dpp_or_zero<0x143, 0xC>(x);
-  return x;
-}
-__device__ __forceinline__ uint32_t wave_from_lane_below(uint32_t x) { return dpp_or_zero<0x138, 0xF>(x); }  // wave_shr:1
-__device__ __forceinline__ uint32_t wave_last_lane(uint32_t x) { return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), kWave - 1)); }
 
 // Line breaks among the lane's 16 bytes.  0x0a and 0x0d differ in exactly their low three bits (010 / 101), so with
 // y = byte ^ 0x0a a line break is y == 0 or y == 7: bits 3..7 clear and bits 0, 1, 2 all equal.  Per dword:

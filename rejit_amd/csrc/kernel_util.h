@@ -1,6 +1,7 @@
 // rejit_amd/csrc/kernel_util.h -- what the kernel translation units that grew out of kernels.hip share (round 6: kernels.hip was
-// 3264 lines and a minute of compile time on its own): wave-level helpers, the hit regions a scanning wave appends to, the span
-// of 1-KiB chunks a wave owns, guarded chunk loads.  Everything lives in an anonymous namespace: every unit gets its own copy.
+// 3264 lines and a minute of compile time on its own): the hit regions a scanning wave appends to, the span of 1-KiB chunks a
+// wave owns, guarded chunk loads.  The wave-level helpers (lane_id, DPP moves, prefix scans) are in wave_ops.h, which every
+// kernel unit includes, with or without this header.  Everything lives in an anonymous namespace: every unit gets its own copy.
 #ifndef REJIT_AMD_KERNEL_UTIL_H_
 #define REJIT_AMD_KERNEL_UTIL_H_
 
@@ -11,37 +12,13 @@
 
 #include "device_program.h"
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace rejit_amd {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kChunk = 1024;  // bytes per wave iteration: 64 lanes x 16 B
-
-__device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
-
-// Cross-lane moves of the dense kernel through DPP (data-parallel primitives: the operand of a VALU
-// instruction comes from another lane of the wave, no LDS crossbar round trip as with ds_bpermute, which
-// is what __shfl_up / __shfl_down compile to).  gfx9 family: row_shr within rows of 16 lanes, row_bcast:15 /
-// row_bcast:31 to carry a row's total into the next rows, wave_shl / wave_shr by one lane.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t x) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROW_MASK, 0xF, true));
-}
-// inclusive prefix sum over the 64 lanes
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
-  x += dpp_or_zero<0x111, 0xF>(x);  // row_shr:1
-  x += dpp_or_zero<0x112, 0xF>(x);  // row_shr:2
-  x += dpp_or_zero<0x114, 0xF>(x);  // row_shr:4
-  x += dpp_or_zero<0x118, 0xF>(x);  // row_shr:8
-  x += dpp_or_zero<0x142, 0xA>(x);  // row_bcast:15 into rows 1 and 3
-  x += dpp_or_zero<0x143, 0xC>(x);  // row_bcast:31 into rows 2 and 3
-  return x;
-}
-__device__ __forceinline__ uint32_t wave_from_lane_below(uint32_t x) { return dpp_or_zero<0x138, 0xF>(x); }  // wave_shr:1, lane 0 gets 0
-__device__ __forceinline__ uint32_t wave_from_lane_above(uint32_t x) { return dpp_or_zero<0x130, 0xF>(x); }  // wave_shl:1, lane 63 gets 0
-__device__ __forceinline__ uint32_t wave_last_lane(uint32_t x) { return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), kWave - 1)); }
 
 // Hit offsets of one wave go to the wave's own REGION of the hit list: region w = wave w,
 // `cap` entries, filled in position order, no atomics.  Every wave owns a contiguous span of

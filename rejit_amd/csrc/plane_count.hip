@@ -42,14 +42,15 @@
 
 #include "exact_count.h"
 #include "kernels.h"
+#include "plane_codes.h"
 #include "short_walk.h"
 #include "stream_load.h"
+#include "wave_ops.h"
 
 namespace rejit_amd {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr uint64_t kBlock = 2048;     // bytes a wave takes per iteration: 64 lanes x 2 pieces of 16 B
 constexpr uint32_t kPieceB = 1024;    // a lane's piece B begins this far behind its piece A
 // Capture (ExactShape): a wave keeps the raw bytes of the last two blocks in LDS -- a block's 2 KiB in text order and, behind
@@ -60,45 +61,8 @@ constexpr uint32_t kStashWords = (2048 + 16) / 4;
 #endif
 constexpr uint32_t kRing = RJ_PC_RING;       // candidate slots per wave; consumed 64 at a time, looked at every second block
 
-__device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
-
-// lane i <- lane i + 1 (wave_shl:1); lane 63 keeps `last`
-__device__ __forceinline__ uint32_t from_lane_above(uint32_t v, uint32_t last) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(last), static_cast<int>(v), 0x130, 0xF, 0xF, false));
-}
-// lane i <- lane i - 1 (wave_shr:1); lane 0 keeps `first`
-__device__ __forceinline__ uint32_t from_lane_below(uint32_t v, uint32_t first) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(first), static_cast<int>(v), 0x138, 0xF, 0xF, false));
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t x) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROW_MASK, 0xF, true));
-}
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
-  x += dpp_or_zero<0x111, 0xF>(x);
-  x += dpp_or_zero<0x112, 0xF>(x);
-  x += dpp_or_zero<0x114, 0xF>(x);
-  x += dpp_or_zero<0x118, 0xF>(x);
-  x += dpp_or_zero<0x142, 0xA>(x);
-  x += dpp_or_zero<0x143, 0xC>(x);
-  return x;
-}
-
-struct Consts {
-  uint32_t cmask;   // 0x03030303 << code_shift
-  uint32_t shift;
-};
-
-// the 2-bit codes of a dword's four bytes as one byte (times 2^shift)
-__device__ __forceinline__ uint32_t codes4(uint32_t d, const Consts& k) { return __builtin_amdgcn_udot4(d & k.cmask, 0x40100401u, 0u, false); }
-
 // the codes of 16 bytes: bits 2k, 2k + 1 = byte k
-__device__ __forceinline__ uint32_t codes16(const uint4& v, const Consts& k) {
+__device__ __forceinline__ uint32_t codes16(const uint4& v, const PlaneCodes& k) {
   const uint32_t s = k.shift;
   return (codes4(v.x, k) >> s) | (codes4(v.y, k) << (8 - s)) | (codes4(v.z, k) << (16 - s)) | (codes4(v.w, k) << (24 - s));
 }
@@ -548,7 +512,7 @@ __device__ __forceinline__ void push_block(WaveState& w, uint32_t hm, uint32_t r
   // (one prefix sum for both: piece A's count in the low half of the word, piece B's in the high half; <= 16 per lane and piece)
   const uint32_t c = __popc(hm_a) | (__popc(hm_b) << 16);
   const uint32_t inc = wave_inclusive_sum(c);
-  const uint32_t tots = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(inc), kWave - 1));
+  const uint32_t tots = wave_last_lane(inc);
   const uint32_t tot_a = tots & 0xFFFFu, tot = tot_a + (tots >> 16);
   if (LIST || tot <= kRing) {   // (ring: more -- the caller's occupancy test voids the run; nothing is written)
     const uint32_t before = inc - c;
@@ -585,7 +549,7 @@ __device__ __forceinline__ void classify_batch(WaveState& w, uint32_t m, const u
   } else {
     S::classify(g, tab, span_base + rel, have, mask, lens);
   }
-  const uint32_t before = from_lane_below(rel, w.prev_rel);
+  const uint32_t before = wave_from_lane_below(rel, w.prev_rel);
   const bool has_before = lane > 0 || w.prev_valid != 0;
   const bool close = have && has_before && (rel - before) < S::lmax(g);
   if (__ballot(close && mask != 0) != 0) {  // (wave-uniform)
@@ -700,7 +664,7 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
   const int lane = lane_id();
   const uint32_t wid = threadIdx.x >> 6;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>((static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6));
-  Consts k;
+  PlaneCodes k;
   k.shift = a.code_shift;
   k.cmask = 0x03030303u << a.code_shift;
   // the blocks are dealt out evenly: wave w takes span_blocks of them, the first span_extra waves one more (a rounded-up
@@ -796,8 +760,8 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
       if (c + 3 <= last_own) load_block(blk(c + 3), lane_rel, rb);
       {
         // (behind lane 63's piece A: lane 0's piece B; behind its piece B: lane 0's piece A of the next block)
-        const uint32_t ha = from_lane_above(xa, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(xb))));
-        const uint32_t hb = from_lane_above(xb, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(ya))));
+        const uint32_t ha = wave_from_lane_above(xa, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(xb))));
+        const uint32_t hb = wave_from_lane_above(xb, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(ya))));
         const uint32_t hm = S::test(xa, xb, ha, hb, g);
         push_block<S::kList, S::kCapture>(w, hm, (c - c0) * static_cast<uint32_t>(kBlock) + lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), c & 1u);
       }
@@ -815,8 +779,8 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
       if (c + 4 <= last_own) load_block(blk(c + 4), lane_rel, ra);
       {
         const uint32_t next0 = c + 2 == fast_end ? behind_codes : static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(xa)));
-        const uint32_t ha = from_lane_above(ya, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(yb))));
-        const uint32_t hb = from_lane_above(yb, next0);
+        const uint32_t ha = wave_from_lane_above(ya, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(yb))));
+        const uint32_t hb = wave_from_lane_above(yb, next0);
         const uint32_t hm = S::test(ya, yb, ha, hb, g);
         push_block<S::kList, S::kCapture>(w, hm, (c + 1 - c0) * static_cast<uint32_t>(kBlock) + lane_rel, (c + 1 - c0) * static_cast<uint32_t>(kBlock), (c + 1) & 1u);
       }
@@ -825,8 +789,8 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
       if (!S::kList && w.tail - w.head >= a.batch_at) blocks_done<S>(w, tab, g, span_base, first_batch);
     }
     if (c + 1 == fast_end) {   // an odd block left: x holds its codes; behind it the span ends
-      const uint32_t ha = from_lane_above(xa, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(xb))));
-      const uint32_t hb = from_lane_above(xb, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(behind_codes))));
+      const uint32_t ha = wave_from_lane_above(xa, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(xb))));
+      const uint32_t hb = wave_from_lane_above(xb, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(behind_codes))));
       const uint32_t hm = S::test(xa, xb, ha, hb, g);
       spill_put(c, behind.x, behind.y);
       push_block<S::kList, S::kCapture>(w, hm, (c - c0) * static_cast<uint32_t>(kBlock) + lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), c & 1u);

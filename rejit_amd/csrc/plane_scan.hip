@@ -43,22 +43,16 @@ RJ_TRACE_EXPORT(rj_debug_trace_plane)
 #include <type_traits>
 
 #include "device_program.h"
+#include "kernel_util.h"
 #include "kernels.h"
+#include "plane_codes.h"
 #include "short_walk.h"
 
 namespace rejit_amd {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr uint64_t kChunk = 1024;   // bytes of one chunk: 64 lanes x 16 B
-constexpr uint64_t kPair = 2048;    // two chunks per wave iteration (the planes interleave them)
-
-__device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
+constexpr uint64_t kPair = 2048;    // two chunks (kernel_util.h: kChunk) per wave iteration (the planes interleave them)
 
 // 16 B of the lane + the 8 B that follow (the neighbour lane's first bytes: same cache lines, L1 hits)
 __device__ __forceinline__ void load_chunk24(const uint8_t* text, uint64_t at, uint32_t (&d)[6]) {
@@ -68,33 +62,10 @@ __device__ __forceinline__ void load_chunk24(const uint8_t* text, uint64_t at, u
   d[4] = h.x; d[5] = h.y;
 }
 
-__device__ __forceinline__ void load_guarded24(const uint8_t* text, uint64_t n, uint64_t at, uint32_t (&d)[6]) {
-#pragma unroll
-  for (int q = 0; q < 6; q++) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint64_t p = at + 4 * q + k;
-      if (p < n) v |= static_cast<uint32_t>(text[p]) << (8 * k);
-    }
-    d[q] = v;
-  }
-}
-
-struct PlaneConsts {
-  uint32_t cmask;   // 0x03030303 << code_shift
-  uint32_t shift;   // code_shift
-};
-
-// the 2-bit codes of a dword's four bytes as one byte (times 2^shift)
-__device__ __forceinline__ uint32_t codes4(uint32_t d, const PlaneConsts& k) {
-  return __builtin_amdgcn_udot4(d & k.cmask, 0x40100401u, 0u, false);
-}
-
 // Candidate positions of one pair of chunks: bit 2k = position k of the lane's 16 bytes of chunk A, bit
 // 2k + 1 = position k of its 16 bytes of chunk B.
 template <int NB>
-__device__ __forceinline__ uint32_t plane_candidates(const uint32_t (&dA)[6], const uint32_t (&dB)[6], const PlaneConsts& k,
+__device__ __forceinline__ uint32_t plane_candidates(const uint32_t (&dA)[6], const uint32_t (&dB)[6], const PlaneCodes& k,
                                                      const PlaneParams& a) {
   const uint32_t s = k.shift;
   const uint32_t ta = (codes4(dA[0], k) >> s) | (codes4(dA[1], k) << (8 - s)) | (codes4(dA[2], k) << (16 - s)) | (codes4(dA[3], k) << (24 - s));
@@ -135,21 +106,6 @@ struct SharedRegion {
   uint32_t count;  // wave-uniform; keeps counting past cap so that the host can size a retry
 };
 
-// inclusive prefix sum over the wave (DPP row shifts + row broadcasts, see kernels.hip)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t x) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROW_MASK, 0xF, true));
-}
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
-  x += dpp_or_zero<0x111, 0xF>(x);
-  x += dpp_or_zero<0x112, 0xF>(x);
-  x += dpp_or_zero<0x114, 0xF>(x);
-  x += dpp_or_zero<0x118, 0xF>(x);
-  x += dpp_or_zero<0x142, 0xA>(x);
-  x += dpp_or_zero<0x143, 0xC>(x);
-  return x;
-}
-
 // Append the candidates of a pair in position order: all of chunk A (even bits), then all of chunk B.
 // `at` = byte offset of the lane's 16 bytes of chunk A; the slot holds the candidate START (w - bias).
 __device__ __forceinline__ void push_pair(SharedRegion& r, uint32_t hm, uint64_t at, uint64_t bias) {
@@ -172,8 +128,8 @@ __device__ __forceinline__ void push_pair(SharedRegion& r, uint32_t hm, uint64_t
   }
   const uint32_t cA = __popc(hA), cB = __popc(hB);
   const uint32_t incA = wave_inclusive_sum(cA), incB = wave_inclusive_sum(cB);
-  const uint32_t totA = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(incA), kWave - 1));
-  const uint32_t totB = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(incB), kWave - 1));
+  const uint32_t totA = wave_last_lane(incA);
+  const uint32_t totB = wave_last_lane(incB);
   uint32_t idx = r.count + incA - cA;
   for (uint32_t m = hA; m; m &= m - 1, idx++)
     if (idx < r.cap) r.slots[idx] = at + (static_cast<uint32_t>(__builtin_ctz(m)) >> 1) - bias;
@@ -187,7 +143,7 @@ __device__ __forceinline__ void push_pair(SharedRegion& r, uint32_t hm, uint64_t
 // with window bytes beyond the end of the text, where the guarded loads read zeros -- may be reported;
 // classify_shared_multi drops them.  The test for it took more registers than the scan itself.)
 template <int NB>
-__device__ __forceinline__ void plane_pair(const uint32_t (&dA)[6], const uint32_t (&dB)[6], uint64_t at, const PlaneConsts& k,
+__device__ __forceinline__ void plane_pair(const uint32_t (&dA)[6], const uint32_t (&dB)[6], uint64_t at, const PlaneCodes& k,
                                            const PlaneParams& a, SharedRegion& region) {
   const uint32_t hm = plane_candidates<NB>(dA, dB, k, a);
   if (__ballot(hm != 0) == 0) return;  // wave-uniform
@@ -203,7 +159,7 @@ __global__ __launch_bounds__(256) void plane_scan(PlaneParams a) {
       static_cast<uint32_t>((static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6));
   if (wave == 0 && lane < kCntSize)
     for (uint32_t p = 0; p < a.n_zero; p++) a.zero_counters[p][lane] = 0;
-  PlaneConsts k;
+  PlaneCodes k;
   k.shift = a.code_shift;
   k.cmask = 0x03030303u << a.code_shift;
   SharedRegion region{a.hits + wave * a.region_cap, a.region_cap, 0u};
@@ -256,8 +212,8 @@ __global__ __launch_bounds__(256) void plane_scan(PlaneParams a) {
   // tail: the pair(s) that touch the end of the text use guarded byte loads
   for (uint64_t t = fast_end; t < c1; t++) {
     uint32_t dA[6], dB[6];
-    load_guarded24(a.text, a.n, t * kPair + lane_off, dA);
-    load_guarded24(a.text, a.n, t * kPair + kChunk + lane_off, dB);
+    load_guarded(a.text, a.n, t * kPair + lane_off, dA);
+    load_guarded(a.text, a.n, t * kPair + kChunk + lane_off, dB);
     plane_pair<NB>(dA, dB, t * kPair + lane_off, k, a, region);
   }
   if (lane == 0) a.hit_counts[wave] = region.count;
@@ -448,8 +404,8 @@ __device__ __forceinline__ void push_pair_lds(LdsRegion& r, uint32_t hm, uint32_
   }
   const uint32_t cA = __popc(hA), cB = __popc(hB);
   const uint32_t incA = wave_inclusive_sum(cA), incB = wave_inclusive_sum(cB);
-  const uint32_t totA = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(incA), kWave - 1));
-  const uint32_t totB = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(incB), kWave - 1));
+  const uint32_t totA = wave_last_lane(incA);
+  const uint32_t totB = wave_last_lane(incB);
   uint32_t idx = r.count + incA - cA;
   for (uint32_t m = hA; m; m &= m - 1, idx++)
     if (idx < kFusedCap) r.slots[idx] = rel + (static_cast<uint32_t>(__builtin_ctz(m)) >> 1);
@@ -460,7 +416,7 @@ __device__ __forceinline__ void push_pair_lds(LdsRegion& r, uint32_t hm, uint32_
 }
 
 template <int NB>
-__device__ __forceinline__ void plane_pair_lds(const uint32_t (&dA)[6], const uint32_t (&dB)[6], uint32_t rel, const PlaneConsts& k,
+__device__ __forceinline__ void plane_pair_lds(const uint32_t (&dA)[6], const uint32_t (&dB)[6], uint32_t rel, const PlaneCodes& k,
                                                const PlaneParams& a, LdsRegion& region) {
   const uint32_t hm = plane_candidates<NB>(dA, dB, k, a);
   if (__ballot(hm != 0) == 0) return;  // wave-uniform
@@ -558,7 +514,7 @@ __global__ __launch_bounds__(256) void plane_scan_classify(PlaneParams a, Shared
       static_cast<uint32_t>((static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6));
   if (wave == 0 && lane < kCntSize && lane != kCntOverflow && lane != kCntMaxRegion && lane != kCntSharedMax)
     for (uint32_t p = 0; p < a.n_zero; p++) a.zero_counters[p][lane] = 0;
-  PlaneConsts k;
+  PlaneCodes k;
   k.shift = a.code_shift;
   k.cmask = 0x03030303u << a.code_shift;
   LdsRegion region{lds + sh.blob_words + (threadIdx.x >> 6) * kFusedCap, 0u};
@@ -615,8 +571,8 @@ __global__ __launch_bounds__(256) void plane_scan_classify(PlaneParams a, Shared
     plane_pair_lds<NB>(a0, b0, static_cast<uint32_t>((c - c0) * kPair) + lane_rel, k, a, region);
   }
   for (uint64_t t = fast_end; t < c1; t++) {
-    load_guarded24(a.text, a.n, t * kPair + lane_off, a0);
-    load_guarded24(a.text, a.n, t * kPair + kChunk + lane_off, b0);
+    load_guarded(a.text, a.n, t * kPair + lane_off, a0);
+    load_guarded(a.text, a.n, t * kPair + kChunk + lane_off, b0);
     plane_pair_lds<NB>(a0, b0, static_cast<uint32_t>((t - c0) * kPair) + lane_rel, k, a, region);
   }
   // the wave's own LDS stores, then its own LDS loads: in order on the LDS queue, no barrier
@@ -647,7 +603,7 @@ bool launch_plane_scan_classify(const PlaneParams& a, const SharedHits& sh, int 
 namespace {
 
 template <int NB, bool TOL>
-__device__ __forceinline__ uint32_t plane_candidates_general(const uint32_t (&dA)[6], const uint32_t (&dB)[6], const PlaneConsts& k,
+__device__ __forceinline__ uint32_t plane_candidates_general(const uint32_t (&dA)[6], const uint32_t (&dB)[6], const PlaneCodes& k,
                                                              const PlaneGParams& a) {
   const uint32_t s = k.shift;
   const uint32_t ta = (codes4(dA[0], k) >> s) | (codes4(dA[1], k) << (8 - s)) | (codes4(dA[2], k) << (16 - s)) | (codes4(dA[3], k) << (24 - s));
@@ -693,7 +649,7 @@ __global__ __launch_bounds__(256) void plane_scan_general(PlaneGParams a) {
       static_cast<uint32_t>((static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6));
   if (wave == 0 && lane < kCntSize)
     for (uint32_t p = 0; p < a.n_zero; p++) a.zero_counters[p][lane] = 0;
-  PlaneConsts k;
+  PlaneCodes k;
   k.shift = a.code_shift;
   k.cmask = 0x03030303u << a.code_shift;
   SharedRegion region{a.hits + wave * a.region_cap, a.region_cap, 0u};
@@ -742,8 +698,8 @@ __global__ __launch_bounds__(256) void plane_scan_general(PlaneGParams a) {
   }
   for (uint64_t t = fast_end; t < c1; t++) {
     uint32_t dA[6], dB[6];
-    load_guarded24(a.text, a.n, t * kPair + lane_off, dA);
-    load_guarded24(a.text, a.n, t * kPair + kChunk + lane_off, dB);
+    load_guarded(a.text, a.n, t * kPair + lane_off, dA);
+    load_guarded(a.text, a.n, t * kPair + kChunk + lane_off, dB);
     pair(dA, dB, t * kPair + lane_off);
   }
   if (lane == 0) a.hit_counts[wave] = region.count;

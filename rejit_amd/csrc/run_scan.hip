@@ -23,16 +23,14 @@
 
 #include "kernels.h"
 #include "run_scan.h"
+#include "wave_ops.h"
 
 namespace rejit_amd {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr uint32_t kIterBytes = 2048;
 constexpr unsigned long long kNone = ~0ull, kBlocked = ~0ull - 1;
-
-__device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
 
 // which class reads which range, as AND masks in scalar registers (0 / ~0); NR = the compile-time bound of the loop over the
 // plan's ranges (ranges beyond n_ranges are computed and dropped: at most NR / 2 - 1 of them)
@@ -166,44 +164,19 @@ __device__ __forceinline__ void run_iteration_quiet(uint64_t it_base, uint32_t S
 //     smallest "A at or behind the last break" of the lanes since the last lane with a break, its last B the largest "B
 //     behind the last break" of those lanes -- keys (breaks so far << 12 | position) make a plain prefix maximum of both;
 //   * the segments between two breaks of one lane (for_inner) need nothing from outside.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp0(uint32_t x) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(x), CTRL, ROW_MASK, 0xF, true));
-}
-__device__ __forceinline__ uint32_t umax(uint32_t x, uint32_t y) { return x > y ? x : y; }
-__device__ __forceinline__ uint32_t wave_prefix_max(uint32_t x) {   // (inclusive; keys are >= 0: the zero a DPP move leaves is neutral)
-  x = umax(x, dpp0<0x111, 0xF>(x));  // row_shr:1
-  x = umax(x, dpp0<0x112, 0xF>(x));  // row_shr:2
-  x = umax(x, dpp0<0x114, 0xF>(x));  // row_shr:4
-  x = umax(x, dpp0<0x118, 0xF>(x));  // row_shr:8
-  x = umax(x, dpp0<0x142, 0xA>(x));  // row_bcast:15 into rows 1 and 3
-  x = umax(x, dpp0<0x143, 0xC>(x));  // row_bcast:31 into rows 2 and 3
-  return x;
-}
-__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t x) {
-  x += dpp0<0x111, 0xF>(x);
-  x += dpp0<0x112, 0xF>(x);
-  x += dpp0<0x114, 0xF>(x);
-  x += dpp0<0x118, 0xF>(x);
-  x += dpp0<0x142, 0xA>(x);
-  x += dpp0<0x143, 0xC>(x);
-  return x;
-}
-__device__ __forceinline__ uint32_t lane_below(uint32_t x) { return dpp0<0x138, 0xF>(x); }   // wave_shr:1, lane 0 gets 0
-__device__ __forceinline__ uint32_t last_lane(uint32_t x) { return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), kWave - 1)); }
 // RunPlan::lag (`A L+`, `A L+ B`): the start stream becomes the marks "A at p - 1 and L at p"; prev_a = the A bit of the byte before
 // the iteration (in: of this one, out: of the next)
 __device__ __forceinline__ uint32_t lag_marks(uint32_t SA, uint32_t BR, uint32_t& prev_a) {
-  const uint32_t below = lane_below(SA) >> 31;
+  const uint32_t below = wave_from_lane_below(SA) >> 31;
   const uint32_t cin = lane_id() == 0 ? prev_a : below;
-  prev_a = last_lane(SA) >> 31;
+  prev_a = wave_last_lane(SA) >> 31;
   return ((SA << 1) | cin) & ~BR;   // (BR holds the text's end: no mark there or beyond)
 }
 // RunPlan::bol (`^` in front): "the byte before p is a line break, or p is the text's begin"; prev_nl as prev_a
 __device__ __forceinline__ uint32_t bol_stream(uint32_t SNL, uint32_t& prev_nl) {
-  const uint32_t below = lane_below(SNL) >> 31;
+  const uint32_t below = wave_from_lane_below(SNL) >> 31;
   const uint32_t cin = lane_id() == 0 ? prev_nl : below;
-  prev_nl = last_lane(SNL) >> 31;
+  prev_nl = wave_last_lane(SNL) >> 31;
   return (SNL << 1) | cin;
 }
 // ... and at a tile's begin: the two carries from the two bytes before the tile (every lane reads the same 32 bytes, once per tile;
@@ -222,11 +195,6 @@ __device__ __forceinline__ void run_entry(const RunParams& a, const RunMasks<NR>
   if (a.plan.bol) a1 &= snl & 1u;               // ... a start only behind a line break (base - 2)
   prev_a = a.plan.lag ? a1 : 0u;
   prev_nl = a.plan.bol ? (snl >> 1) & 1u : 0u;
-}
-__device__ __forceinline__ unsigned long long lane_value(unsigned long long x, int l) {
-  const uint32_t lo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(x)), l));
-  const uint32_t hi = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<uint32_t>(x >> 32)), l));
-  return (static_cast<unsigned long long>(hi) << 32) | lo;
 }
 __device__ __forceinline__ uint32_t bits_below(uint32_t b) { return (1u << b) - 1u; }        // b in 0 .. 31
 __device__ __forceinline__ uint32_t bits_upto(uint32_t b) { return (2u << b) - 1u; }         // bits 0 .. b, b in 0 .. 31
@@ -248,16 +216,16 @@ __device__ __forceinline__ LaneClose run_iteration_par(uint64_t it_base, uint32_
   const uint32_t headB = hb ? SB & bits_upto(fb) : SB;       // (B may be the break itself)
   const uint32_t tailA = hb ? SA & ~bits_below(lb) : SA;     // (a start may sit ON the break that opens its segment)
   const uint32_t tailB = hb ? SB & ~bits_upto(lb) : SB;
-  const uint32_t seg_excl = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(brm >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(brm), 0u));
+  const uint32_t seg_excl = lanes_below(brm);
   const uint32_t seg_incl = seg_excl + (hb ? 1u : 0u);
   const uint32_t keyA = (seg_incl << 12) | (tailA ? 0xfffu - (pbase + static_cast<uint32_t>(__builtin_ctz(tailA))) : 0u);
-  const uint32_t inclA = wave_prefix_max(keyA);
-  const uint32_t exclA = lane_below(inclA) & 0xfffu;
+  const uint32_t inclA = wave_inclusive_max(keyA);
+  const uint32_t exclA = wave_from_lane_below(inclA) & 0xfffu;
   uint32_t inclB = 0, exclB = 0;
   if (HAS_B) {
     const uint32_t keyB = (seg_incl << 12) | (tailB ? pbase + 32u - static_cast<uint32_t>(__builtin_clz(tailB)) : 0u);   // position + 1
-    inclB = wave_prefix_max(keyB);
-    exclB = lane_below(inclB) & 0xfffu;
+    inclB = wave_inclusive_max(keyB);
+    exclB = wave_from_lane_below(inclB) & 0xfffu;
   }
   LaneClose c;
   c.s = c.q = c.b_any = kNone;
@@ -285,7 +253,7 @@ __device__ __forceinline__ LaneClose run_iteration_par(uint64_t it_base, uint32_
     }
   }
   // behind the iteration's last break
-  const uint32_t endA = last_lane(inclA) & 0xfffu, endB = last_lane(inclB) & 0xfffu;
+  const uint32_t endA = wave_last_lane(inclA) & 0xfffu, endB = wave_last_lane(inclB) & 0xfffu;
   st.s = endA != 0 ? it_base + (0xfffu - endA) : kNone;
   st.q = (endA != 0 && endB != 0 && it_base + (endB - 1u) > st.s) ? it_base + (endB - 1u) : kNone;
   return c;
@@ -382,7 +350,7 @@ __global__ __launch_bounds__(256) void run_summary(RunParams a) {
         const uint64_t at = it_base + static_cast<uint64_t>(lane) * 32u + s;
         if (at >= a.sb && at < a.se && (!eol || ((SNL >> r) & 1u) != 0)) inner++;
       });
-      cnt += last_lane(wave_prefix_sum(inner));
+      cnt += wave_total(inner);
     }
   }
   if (before_first) {   // no break in the tile
@@ -634,7 +602,7 @@ __global__ __launch_bounds__(256) void run_emit(RunParams a) {
         if (word + s >= a.sb && word + s < a.se && (!eol || ((SNL >> r) & 1u) != 0)) mine++;
       });
     if (__ballot(mine != 0) == 0) continue;
-    const uint32_t inc = wave_prefix_sum(mine);
+    const uint32_t inc = wave_inclusive_sum(mine);
     unsigned long long idx = pos + inc - mine;
     if (first) {
       if (idx < a.out_cap) *reinterpret_cast<ulonglong2*>(a.out + 2 * idx) = make_ulonglong2(c.s - a.plan.lag, HAS_B ? c.q + 1 : word + static_cast<uint32_t>(__builtin_ctz(BR)));
@@ -647,7 +615,7 @@ __global__ __launch_bounds__(256) void run_emit(RunParams a) {
           idx++;
         }
       });
-    pos += last_lane(inc);
+    pos += wave_last_lane(inc);
   }
 }
 
@@ -773,8 +741,7 @@ __device__ __forceinline__ void pair_streams_of(const RunParams& a, const RunMas
   *SQ = sa;
   *RS = br & ~sa;   // (every Q is a break: no Q lies inside L)
 }
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
-__device__ __forceinline__ uint32_t wave_total(uint32_t x) { return last_lane(wave_prefix_sum(x)); }
+__device__ __forceinline__ uint64_t lane_mask_below(int lane) { return (1ull << lane) - 1ull; }
 
 }  // namespace
 
@@ -822,8 +789,8 @@ __global__ __launch_bounds__(256) void pair_summary(RunParams a) {
     }
     // resets: F = the Q bytes of the iteration below its first reset, Lq = below its last one; between the two every
     // segment (from one reset to the next) closes n / 2 pairs: (Lq - F - the number of odd segments) / 2 in all
-    const uint32_t inc = wave_prefix_sum(nq);
-    const uint32_t T = last_lane(inc);
+    const uint32_t inc = wave_inclusive_sum(nq);
+    const uint32_t T = wave_last_lane(inc);
     const int j1 = __builtin_ctzll(rm), jl = 63 - __builtin_clzll(rm);
     const bool hr = RS != 0;
     const uint32_t fr = hr ? static_cast<uint32_t>(__builtin_ctz(RS)) : 0u, lr = hr ? 31u - static_cast<uint32_t>(__builtin_clz(RS)) : 0u;
@@ -833,7 +800,7 @@ __global__ __launch_bounds__(256) void pair_summary(RunParams a) {
     const uint32_t F = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(ev), j1));
     const uint32_t Lq = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(sv), jl));
     const uint64_t S = __ballot(hr && (sv & 1u) != 0);
-    const uint64_t lower = rm & lanes_below(lane);
+    const uint64_t lower = rm & lane_mask_below(lane);
     bool odd = false;
     if (hr && lower != 0) {   // the segment the lane's first reset closes began behind the last reset of lane i
       const int i = 63 - __builtin_clzll(lower);
@@ -949,8 +916,8 @@ __global__ __launch_bounds__(256) void pair_emit(RunParams a) {
       continue;
     }
     const uint32_t nq = static_cast<uint32_t>(__popc(SQ));
-    const uint32_t inc = wave_prefix_sum(nq);
-    const uint32_t T = last_lane(inc);
+    const uint32_t inc = wave_inclusive_sum(nq);
+    const uint32_t T = wave_last_lane(inc);
     // the lane's incoming parity: the Q bytes between the last reset below its word (or the iteration's begin, the carried
     // bit counted) and its word
     uint32_t ip = ((inc - nq) ^ (open ? 1u : 0u)) & 1u;
@@ -961,7 +928,7 @@ __global__ __launch_bounds__(256) void pair_emit(RunParams a) {
       const uint32_t qa = hr ? static_cast<uint32_t>(__popc(SQ & ~bits_upto(lr))) : nq;
       const uint32_t sv = inc - qa;
       const uint64_t S = __ballot(hr && (sv & 1u) != 0);
-      const uint64_t lower = rm & lanes_below(lane);
+      const uint64_t lower = rm & lane_mask_below(lane);
       if (lower != 0) {
         const int i = 63 - __builtin_clzll(lower);
         ip = ((inc - nq) ^ static_cast<uint32_t>(S >> i)) & 1u;
@@ -994,12 +961,12 @@ __global__ __launch_bounds__(256) void pair_emit(RunParams a) {
     if (__ballot(mine != 0) == 0) continue;
     // the opener of a lane's first closer, when it lies below the lane's word: the last Q of the lanes below, else the carried one
     const uint32_t topq = SQ != 0 ? 31u - static_cast<uint32_t>(__builtin_clz(SQ)) : 0u;
-    const uint64_t lowerq = qm & lanes_below(lane);
+    const uint64_t lowerq = qm & lane_mask_below(lane);
     const int pl = lowerq != 0 ? 63 - __builtin_clzll(lowerq) : 0;
     const uint32_t tq = static_cast<uint32_t>(__shfl(static_cast<int>(topq), pl));
     const unsigned long long below_at = lowerq != 0 ? it_base + static_cast<uint32_t>(pl) * 32u + tq : carried_at;
     const uint64_t word = it_base + static_cast<uint64_t>(lane) * 32u;
-    const uint32_t incm = wave_prefix_sum(mine);
+    const uint32_t incm = wave_inclusive_sum(mine);
     unsigned long long idx = pos + incm - mine;
     for (uint32_t m = closers; m != 0; m &= m - 1u) {
       const uint32_t b = static_cast<uint32_t>(__builtin_ctz(m));
@@ -1008,7 +975,7 @@ __global__ __launch_bounds__(256) void pair_emit(RunParams a) {
       if (idx < a.out_cap) *reinterpret_cast<ulonglong2*>(a.out + 2 * idx) = make_ulonglong2(begin, word + b + 1u);
       idx++;
     }
-    pos += last_lane(incm);
+    pos += wave_last_lane(incm);
   }
 }
 

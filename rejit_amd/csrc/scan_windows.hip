@@ -179,11 +179,6 @@ __device__ __forceinline__ void windows_chunk(const uint32_t (&d)[6], uint64_t a
   hits.push_bits(hm, at, ws.offset);
 }
 
-// lane i <- lane i + 1 (wave_shl:1); lane 63 keeps `last`
-__device__ __forceinline__ uint32_t lane_above_or(uint32_t v, uint32_t last) {
-  return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(last), static_cast<int>(v), 0x130, 0xF, 0xF, false));
-}
-
 template <bool TWO>
 __device__ __forceinline__ void load_chunk(const uint8_t* text, uint64_t at, uint32_t (&d)[6]) {
   const uint4 v = *reinterpret_cast<const uint4*>(text + at);   // (default policy: the halo load below asks for the same lines)
@@ -231,8 +226,8 @@ __device__ __forceinline__ void scan_windows_body(const ScanParams& a, const Win
     auto proc = [&](const uint4& q, uint32_t nx, uint32_t ny, uint64_t c) __attribute__((always_inline)) {
       uint32_t d[6];
       d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
-      d[4] = lane_above_or(q.x, nx);
-      d[5] = TWO ? lane_above_or(q.y, ny) : 0u;
+      d[4] = wave_from_lane_above(q.x, nx);
+      d[5] = TWO ? wave_from_lane_above(q.y, ny) : 0u;
       windows_chunk<K, TWO, MASKED, TWOLEVEL, NIB>(d, c * kChunk + lane_off, a, ws, hits);
     };
     auto first_of = [](uint32_t v) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(v))); };
@@ -273,7 +268,7 @@ __device__ __forceinline__ void scan_windows_body(const ScanParams& a, const Win
       if (lane == kWave - 1) h = *reinterpret_cast<const uint2*>(a.text + (c + 1) * kChunk);
       const uint4 cur = q0;
       if (c + 1 < fast_end) q0 = ld(c + 1);
-      proc(cur, h.x, h.y, c);   // (lane 63 keeps its own h: lane_above_or's `last` is per lane)
+      proc(cur, h.x, h.y, c);   // (lane 63 keeps its own h: wave_from_lane_above's `fill` is per lane)
     }
   }
   // tail: the chunk(s) that touch the end of the text use guarded byte loads

@@ -28,18 +28,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wave_ops.h"
+
 namespace rejit_amd {
 namespace lookback {
 
 constexpr uint32_t kSpinLimit = 1u << 22;
-constexpr int kWave = 64;
 constexpr uint64_t kGroup = 64;                           // units per group
 constexpr unsigned long long kHave = 1ull << 62;          // units[], prefix[]: the word has been written
 constexpr unsigned long long kValueMask = (1ull << 62) - 1;
 constexpr int kArrivalShift = 56;                         // groups[]: arrivals << 56 | sum of the counts
 constexpr unsigned long long kSumMask = (1ull << kArrivalShift) - 1;
-
-__device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
 
 // words a run of n_units units needs: units[n_units], groups[n_groups], prefix[n_groups] -- all zero at the start
 __host__ __device__ inline uint64_t n_groups(uint64_t n_units) { return (n_units + kGroup - 1) / kGroup; }

@@ -35,18 +35,16 @@ RJ_TRACE_EXPORT(rj_debug_trace_lds)
 #include "device_program.h"
 #include "kernels.h"
 #include "lds_walk.h"
+#include "wave_ops.h"
 
 namespace rejit_amd {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr uint32_t kRegionsPerBlock = 32;  // (64: a fifth of the workgroups of a 1000-hit run had more regions with hits than waves; 16: no faster)
 constexpr uint32_t kWinBytes = 1024;      // floating: text window of a wave (64 lanes x 16 B)
 constexpr uint32_t kLaneWin = 128;        // behind: text window of a lane ...
 constexpr uint32_t kLaneWinStride = 144;  // ... at this stride (16-byte aligned slots, 8 banks apart)
-
-__device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & (kWave - 1); }
 
 // 16 bytes of the text at `at` (16-byte aligned); bytes at or beyond n read as 0.  The partial block at the end of
 // the text is out of line: it is needed once per text at most, and inlined at every use it was most of the code.
@@ -244,8 +242,7 @@ __global__ __launch_bounds__(256) void verify_floating_lds(VerifyParams a, WalkD
             const uint64_t sl = base + static_cast<uint64_t>(l);
             if (sl < cur) continue;
             took |= 1ull << l;
-            cur = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(e >> 32), l))) << 32) |
-                  static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(e), l));
+            cur = lane_value(e, l);
           }
         }
         const uint32_t pos = kept + __popcll(took & ((1ull << sub) - 1ull));
