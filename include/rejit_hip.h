@@ -204,6 +204,38 @@ int rj_scan_stats_sized(const rj_scan* scan, void* stats, size_t struct_size);
 /* 1 / 0 / <0: kMatchFull over device text */
 int rj_scan_match_full(rj_scan* scan, const void* d_text, uint64_t n, void* hip_stream);
 
+/* ---- per-record answers over device-resident text (rejit_amd/csrc/record_join.hip): what a grep-like
+ * or dataframe-like caller wants -- how many matches each record (line, string of a column, text of a packed batch) has, which
+ * records match, where a record's matches sit in the list -- without a download of the list.  Records are
+ * d_text[rec_begin[i], rec_end[i]), ascending and not overlapping: rec_begin[i] <= rec_end[i] <= rec_begin[i + 1], rec_end[last]
+ * <= n; gaps between records are allowed, so are records that touch.  ONE ordinary whole-text run (rj_scan_run(scan, d_text, n,
+ * 0, n + 1, 0, 0, 0, stream)), then every match goes by its BEGIN b to the last record i with rec_begin[i] <= b, and is kept
+ * when b <= rec_end[i] (else it lies in a gap and belongs to no record) -- the rule of rj_match_all_packed: an empty match at a
+ * record's end is that record's when a gap follows, the next record's when the two touch.  A kept match that ends beyond
+ * rec_end[i] still counts for record i and is tallied in n_crossing: the library does not make records independent, the caller's
+ * layout does (every byte outside a record holds rj_batch_separator(prog), as for rj_match_all_packed; n_crossing == 0 tells).
+ * Record i's matches are spans[first[i] .. first[i] + count[i]) of the run's own list, as offsets into d_text. */
+typedef struct {
+  uint64_t n_kept;       /* matches that belong to a record                       */
+  uint64_t n_matching;   /* records with at least one match                       */
+  uint64_t n_crossing;   /* kept matches that end beyond their record's end       */
+  uint64_t n_matches;    /* the whole-text run's matches (kept + in gaps)         */
+} rj_record_stats;
+
+/* d_rec_begin / d_rec_end: device, n_records uint64 each.  d_counts: device, n_records uint32 (saturating at
+ * UINT32_MAX), may be NULL.  d_first: device, n_records uint64, may be NULL.  Returns n_kept or rj_status;
+ * RJ_BAD_ARGUMENT with a message naming the first bad row when the table is not ascending / inside the text.
+ * Afterwards rj_scan_device_spans / _copy_spans / rj_scan_stats are those of the whole-text run.  Every output is written
+ * by exactly one lane: nothing has to be cleared first.  A refusal of the run itself (RJ_TOO_LARGE) passes through. */
+int64_t rj_scan_records(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                        const uint64_t* d_rec_end, uint64_t n_records, uint32_t* d_counts, uint64_t* d_first,
+                        rj_record_stats* stats, void* hip_stream);
+/* indices (ascending) of the records of the LAST rj_scan_records on this scan with a match (invert != 0: without);
+ * d_indices: device, cap uint64; returns how many there are (writes at most cap) or rj_status.  Reads the counts of that
+ * join: the caller's d_counts (which must still hold them) or, when that was NULL, the scan's own copy.  RJ_BAD_ARGUMENT when
+ * the scan's last run was anything but a successful rj_scan_records. */
+int64_t rj_scan_records_select(rj_scan* scan, int invert, uint64_t* d_indices, uint64_t cap, void* hip_stream);
+
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md
  * section 4) the text is read ONCE for all of them; otherwise the patterns run one after another.

@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -157,6 +157,25 @@ class _Stats(ctypes.Structure):
                 ("stream_path", ctypes.c_int32), ("slow_starts", ctypes.c_int32), ("count_path", ctypes.c_int32), ("run_path", ctypes.c_int32)]
 
 
+class _RecordStats(ctypes.Structure):
+    _fields_ = [("n_kept", ctypes.c_uint64), ("n_matching", ctypes.c_uint64), ("n_crossing", ctypes.c_uint64), ("n_matches", ctypes.c_uint64)]
+
+
+class RecordsResult:
+    """What Scan.run_records returns: rj_record_stats (n_kept, n_matching, n_crossing, n_matches) and the per-record tensors --
+    counts (int32: the library's uint32, saturating, so 2^32 - 1 reads -1) and first (int64), both on the text's device.
+    Record i's matches are spans[first[i] : first[i] + counts[i]] of the scan's own list (Scan.spans_tensor)."""
+
+    def __init__(self, stats: _RecordStats, counts, first, n_records: int):
+        self.n_kept, self.n_matching = int(stats.n_kept), int(stats.n_matching)
+        self.n_crossing, self.n_matches = int(stats.n_crossing), int(stats.n_matches)
+        self.counts, self.first, self.n_records = counts, first, n_records
+
+    def __repr__(self):
+        return "RecordsResult(n_records=%d, n_kept=%d, n_matching=%d, n_crossing=%d, n_matches=%d)" % (
+            self.n_records, self.n_kept, self.n_matching, self.n_crossing, self.n_matches)
+
+
 _lib = None
 
 # every symbol include/rejit_hip.h declares
@@ -175,7 +194,8 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds", "rj_batch_separator", "rj_match_all_packed", "rj_host_alloc", "rj_host_free",
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
-                 "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch"]
+                 "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
+                 "rj_scan_records", "rj_scan_records_select"]
 
 
 def load_library():
@@ -273,6 +293,10 @@ def load_library():
     L.rj_host_alloc.restype = vp
     L.rj_host_alloc.argtypes = [sz]
     L.rj_host_free.argtypes = [vp]
+    L.rj_scan_records.restype = i64
+    L.rj_scan_records.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, ctypes.POINTER(_RecordStats), vp]
+    L.rj_scan_records_select.restype = i64
+    L.rj_scan_records_select.argtypes = [vp, ctypes.c_int, vp, u64, vp]
     _lib = L
     return L
 
@@ -538,6 +562,51 @@ class Scan:
         assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
         st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
         return self.run(t.data_ptr(), int(t.numel() if n is None else n), stream=st, **kw)
+
+    def run_records(self, text_tensor, rec_begin, rec_end, counts=None, first=None, stream=None) -> RecordsResult:
+        """rj_scan_records: one whole-text run over `text_tensor` (contiguous uint8 on the GPU), its matches handed to the
+        records text[rec_begin[i], rec_end[i]) -- int64 tensors on the same device, ascending, not overlapping (gaps allowed).
+        counts (int32) / first (int64): tensors of the caller's to write into, else new ones.  spans() / spans_tensor() /
+        stats() afterwards are those of the whole-text run."""
+        import torch
+
+        t = text_tensor
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        k = int(rec_begin.numel())
+        for x in (rec_begin, rec_end):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == k
+        if counts is None:
+            counts = torch.empty(k, dtype=torch.int32, device=t.device)
+        if first is None:
+            first = torch.empty(k, dtype=torch.int64, device=t.device)
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.device == t.device and counts.numel() == k
+        assert first.dtype == torch.int64 and first.is_contiguous() and first.device == t.device and first.numel() == k
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        rs = _RecordStats()
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if k else 0)
+        _check(self._lib.rj_scan_records(self._h, ctypes.c_void_p(t.data_ptr()), int(t.numel()), ptr(rec_begin), ptr(rec_end), k,
+                                         ptr(counts), ptr(first), ctypes.byref(rs), ctypes.c_void_p(st)))
+        self._records = (t.device, k, counts, st)   # (the selection reads these counts: kept alive)
+        return RecordsResult(rs, counts, first, k)
+
+    def select_records(self, invert: bool = False, cap: Optional[int] = None, stream=None):
+        """rj_scan_records_select: the ascending indices (int64 tensor on the text's device) of the records of the last
+        run_records with a match -- invert: without one.  cap: write at most that many (the tensor is then cap long at most);
+        self.n_selected holds the full number."""
+        import torch
+
+        rec = getattr(self, "_records", None)
+        if rec is None:
+            # (no run_records yet: the library refuses, with its own message)
+            _check(self._lib.rj_scan_records_select(self._h, int(invert), None, 0, None))
+            raise RejitError(-4, "select_records without run_records")
+        device, k, _counts, st0 = rec
+        room = k if cap is None else min(int(cap), k)
+        out = torch.empty(max(room, 1), dtype=torch.int64, device=device)
+        st = st0 if stream is None else stream
+        total = int(_check(self._lib.rj_scan_records_select(self._h, int(invert), ctypes.c_void_p(out.data_ptr()), room, ctypes.c_void_p(st))))
+        self.n_selected = total
+        return out[:min(total, room)]
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""

@@ -1077,6 +1077,7 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
   s->result = nullptr;
   s->result_count = 0;
   s->want_exact = false;
+  s->rec_valid = false;   // (rj_scan_records_select answers for the last run only when that was rj_scan_records)
   if (sb >= se) return RJ_OK;
   if ((reinterpret_cast<uintptr_t>(d_text) & 15u) != 0) return fail(RJ_BAD_ARGUMENT, "device text must be 16-byte aligned");
   const auto wall0 = std::chrono::steady_clock::now();
@@ -1330,6 +1331,7 @@ void rj_scan_destroy(rj_scan* s) {
   if (s->small_hdr) (void)hipHostFree(s->small_hdr);
   if (s->small_text) (void)hipHostFree(s->small_text);
   if (s->gx_host) (void)hipHostFree(s->gx_host);
+  if (s->rec_host) (void)hipHostFree(s->rec_host);
   for (auto& e : s->ev)
     if (e) (void)hipEventDestroy(e);
   if (s->own_stream) (void)hipStreamDestroy(s->own_stream);
@@ -1363,6 +1365,7 @@ static int scan_start(rj_scan* s, const void* d_text, uint64_t n, void* hip_stre
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   s->pending = true;
   s->pending_launched = false;
+  s->rec_valid = false;
   s->pending_text = static_cast<const uint8_t*>(d_text);
   s->pending_n = n;
   s->pending_stream = st;

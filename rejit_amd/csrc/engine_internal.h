@@ -165,6 +165,13 @@ struct rj_scan {
   // scan_count); state 0 not looked at yet, 1 the pattern has the shape, -1 it has not
   struct rj_multi* counter = nullptr;
   int counter_state = 0;
+  // rj_scan_records / rj_scan_records_select (record_join.hip): the join's summary (device + pinned copy), the counts when the
+  // caller kept none, the selection's look-back words; rec_valid: the scan's last run was a successful rj_scan_records
+  rejit_amd::DeviceBuffer rec_summary, rec_counts, rec_granules;
+  unsigned long long* rec_host = nullptr;
+  const uint32_t* rec_select_counts = nullptr;
+  uint64_t rec_n = 0;
+  bool rec_valid = false;
 };
 
 namespace rejit_amd {

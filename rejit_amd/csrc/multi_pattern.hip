@@ -1663,6 +1663,7 @@ int rj_multi_set_counts_only(rj_multi* m, int on) {
 // rj_multi of the one pattern on the counts path, made at the first call; patterns without the shape (or a void run) are
 // answered by the scan's own pipeline.
 int64_t rejit_amd::scan_count(rj_scan* s, const uint8_t* d_text, uint64_t n, hipStream_t st) {
+  s->rec_valid = false;
   if (s->counter_state == 0) {
     s->counter_state = -1;
     const rj_program* progs[1] = {s->prog};

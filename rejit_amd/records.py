@@ -1,0 +1,58 @@
+"""Record tables for Scan.run_records (rj_scan_records, include/rejit_hip.h): torch plumbing only -- every table is built
+from device tensors, the matching and the join are the library's kernels."""
+from __future__ import annotations
+
+from typing import List, Sequence, Tuple
+
+from .api import Program, Scan
+
+
+def line_records(text_tensor, stream=None):
+    """(rec_begin, rec_end): the lines of `text_tensor` (contiguous uint8 on the GPU) as int64 device tensors.  The begins
+    are the matches of `^` (a MatchAll on the device, emit_scan.hip: the line table of a grep-like caller); a line ends
+    before its line break, the last one at the end of the text.  A text that ends in a line break has a last, empty line
+    behind it, exactly as `^` sees it."""
+    import torch
+
+    n = int(text_tensor.numel())
+    scan = Scan(Program(b"^"))
+    scan.run_tensor(text_tensor, stream=stream)
+    begins = scan.spans_tensor(text_tensor.device)[:, 0].contiguous()
+    ends = torch.empty_like(begins)
+    if begins.numel():
+        ends[:-1] = begins[1:] - 1     # (the byte before the next line's begin is this line's break)
+        ends[-1] = n
+    return begins, ends
+
+
+def pack_records(texts: Sequence[bytes], sep: int, device, lead: int = 0, gap: int = 1):
+    """(text_tensor, rec_begin, rec_end) on `device`: the packed layout of rj_match_all_packed -- `lead` separator bytes, then
+    every text followed by `gap` >= 1 bytes of `sep` (Program.batch_separator()), so that no match crosses a record."""
+    import numpy as np
+    import torch
+
+    assert gap >= 1 and 0 <= sep < 256
+    sizes = np.array([len(t) for t in texts], dtype=np.int64)
+    begins = lead + np.concatenate([[0], np.cumsum(sizes + gap)[:-1]]).astype(np.int64) if len(texts) else np.zeros(0, dtype=np.int64)
+    total = lead + int(sizes.sum()) + gap * len(texts)
+    buf = np.full(max(total, 1), sep, dtype=np.uint8)
+    for b, t in zip(begins, texts):
+        buf[b:b + len(t)] = np.frombuffer(t, dtype=np.uint8)
+    text = torch.from_numpy(buf[:total].copy() if total else buf[:0].copy()).to(device)
+    return text, torch.from_numpy(begins).to(device), torch.from_numpy(begins + sizes).to(device)
+
+
+def relative_spans(spans, result, rec_begin, i: int):
+    """Record i's matches relative to its begin: an (count, 2) int64 tensor -- spans = the scan's spans_tensor after
+    run_records, result = what run_records returned."""
+    f, c = int(result.first[i]), int(result.counts[i]) & 0xFFFFFFFF
+    return spans[f:f + c] - rec_begin[i]
+
+
+def all_relative_spans(spans, result, rec_begin) -> List[List[Tuple[int, int]]]:
+    """Every record's matches relative to its begin, as Python lists (tests, small tables)."""
+    sp = spans.cpu().tolist()
+    out = []
+    for f, c, b in zip(result.first.cpu().tolist(), result.counts.cpu().tolist(), rec_begin.cpu().tolist()):
+        out.append([(x - b, y - b) for x, y in sp[f:f + (c & 0xFFFFFFFF)]])
+    return out

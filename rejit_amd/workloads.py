@@ -227,6 +227,31 @@ def random_ascii_torch(n: int, seed: int, device, lo: int = ord("0"), hi: int = 
     return out
 
 
+def _log_like_table() -> np.ndarray:
+    """256 symbols in the proportions of tools/probes/zoo.py's text: lower-case letters common, capitals / digits / punctuation
+    rarer, a blank in 14 bytes, a line break in 64."""
+    t = b"etaoinshrdlucmfwypvbgkqjxz" * 7 + b"etao" * 2 + b"0123456789" + b" " * 18 + b".,:;=-_/@()<>\"'#" + b"ETAOINSHR" * 2 + b"\n" * 4
+    assert len(t) == 256
+    return np.frombuffer(t, dtype=np.uint8).copy()
+
+
+def log_like_numpy(n: int, seed: int, start: int = 0) -> np.ndarray:
+    """bytes[start : start+n] of a seeded stream of synthetic log / source-like text (words, numbers, punctuation, lines of
+    64 bytes on average, empty lines among them)."""
+    return _log_like_table()[random_ascii_numpy(n, seed, lo=0, hi=256, start=start)]
+
+
+def log_like_torch(n: int, seed: int, device, start: int = 0):
+    """The same stream as log_like_numpy, generated on `device`."""
+    import torch
+
+    table = torch.from_numpy(_log_like_table()).to(device)
+    out = random_ascii_torch(n, seed, device, lo=0, hi=256, start=start)
+    for a in range(0, n, 1 << 28):   # (in place, chunk by chunk: the index tensor of a gather is int64)
+        out[a:a + (1 << 28)] = table[out[a:a + (1 << 28)].long()]
+    return out
+
+
 def plant_offsets(n: int, length: int, count: int, seed: int, boundaries: Sequence[int] = ()) -> List[int]:
     """`count` sorted, pairwise non-overlapping, non-adjacent offsets for planted
     occurrences: offset 0, the very end, a back-to-back pair, one straddling each

@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] -- count or number the lines of FILE in which a match of PATTERN begins, the
+way `grep -E -c` / `grep -E -n | cut -d: -f1` do, with everything between the upload and the answer on the GPU:
+
+    the file is uploaded once; `^` over it is the line table (rejit_amd/records.py: line_records), PATTERN over it the match
+    list, rj_scan_records joins the two on the device and rj_scan_records_select lists the lines -- only the four-word
+    summary (-c) or the selected line numbers (-n) come back.
+
+  -c   print the number of selected lines (the default)
+  -n   print their 1-based numbers, one per line
+  -v   select the lines WITHOUT a match
+
+Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
+its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
+line break the output is grep's.  samples/jrep_gpu.* is the full grep (files, context, -H); this is the per-record API in
+forty lines."""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def main(argv):
+    flags = [a for a in argv if a in ("-c", "-v", "-n")]
+    rest = [a for a in argv if a not in ("-c", "-v", "-n")]
+    if len(rest) != 2:
+        sys.stderr.write(__doc__)
+        return 2
+    path, pattern = rest
+    invert, numbers = "-v" in flags, "-n" in flags and "-c" not in flags
+    import numpy as np
+    import torch
+
+    import rejit_amd
+    from rejit_amd import records
+
+    if not torch.cuda.is_available():
+        sys.stderr.write("linegrep_gpu: no GPU\n")
+        return 2
+    rejit_amd.build()
+    data = np.fromfile(path, dtype=np.uint8)
+    if data.size == 0:
+        if not numbers:
+            print(0)
+        return 1
+    text = torch.from_numpy(data).to("cuda:0")                       # the only upload
+    begins, ends = records.line_records(text)
+    if data[-1] in (10, 13):                                         # `^` also matches behind the file's last line break: not a line
+        begins, ends = begins[:-1].contiguous(), ends[:-1].contiguous()
+    scan = rejit_amd.Scan(rejit_amd.Program(pattern))
+    result = scan.run_records(text, begins, ends)
+    selected = result.n_records - result.n_matching if invert else result.n_matching
+    if numbers:
+        lines = scan.select_records(invert=invert)                   # the only download besides the summary
+        sys.stdout.write("".join("%d\n" % (i + 1) for i in lines.cpu().tolist()))
+    else:
+        print(selected)
+    return 0 if selected else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
