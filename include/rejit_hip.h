@@ -235,6 +235,26 @@ int64_t rj_scan_records(rj_scan* scan, const void* d_text, uint64_t n, const uin
  * join: the caller's d_counts (which must still hold them) or, when that was NULL, the scan's own copy.  RJ_BAD_ARGUMENT when
  * the scan's last run was anything but a successful rj_scan_records. */
 int64_t rj_scan_records_select(rj_scan* scan, int invert, uint64_t* d_indices, uint64_t cap, void* hip_stream);
+/* Records of a device text gathered into a NEW contiguous device text (rejit_amd/csrc/record_pack.hip):
+ * what a grep-like caller prints (the selected lines, fill = '\n') and what makes the strings of a column whose records touch
+ * independent (fill = rj_batch_separator(prog)) -- without a download.  With k = d_indices ? n_indices : n_records,
+ * r(j) = d_indices ? d_indices[j] : j and len(j) = rec_end[r(j)] - rec_begin[r(j)]:
+ *     ob(0) = lead, ob(j + 1) = ob(j) + len(j) + gap, total = ob(k)       (k == 0: total = lead)
+ *     d_out[ob(j), ob(j) + len(j)) = the bytes of text record r(j); every other byte of d_out[0, total) = fill
+ *     d_out_begin[j] = ob(j), d_out_end[j] = ob(j) + len(j)               (k uint64 each; either may be NULL)
+ * d_indices: any order, repeats allowed (a permutation, a take; rj_scan_records_select's output is the common case); a
+ * non-NULL d_indices with n_indices == 0 packs nothing.  Rows need not be in order with each other; every packed row must
+ * keep begin <= end <= n and every index must be < n_records: RJ_BAD_ARGUMENT with a message naming the first bad j -- a bad
+ * row is never followed outside the text or the output.  fill: 0..255; gap may be 0.  d_out: 16-byte aligned, out_cap
+ * bytes, not overlapping the text.  Returns total WHATEVER out_cap is and never writes at or beyond out_cap; d_out == NULL
+ * with out_cap == 0 is the size query (the tables are still written when given).  With total <= out_cap the result is
+ * complete: every byte of [0, total) and every table row is written exactly once, nothing has to be cleared first, nothing
+ * behind total is touched.  n + gap must stay below 2^42 and lead + k * (n + gap) below 2^62.  The scan lends scratch only: its span list, its
+ * stats and the state of its last rj_scan_records (rj_scan_records_select included) stay as they were. */
+int64_t rj_scan_records_pack(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                             const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
+                             int fill, uint64_t lead, uint64_t gap, void* d_out, uint64_t out_cap, uint64_t* d_out_begin,
+                             uint64_t* d_out_end, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

@@ -168,6 +168,9 @@ struct rj_scan {
   // rj_scan_records / rj_scan_records_select (record_join.hip): the join's summary (device + pinned copy), the counts when the
   // caller kept none, the selection's look-back words; rec_valid: the scan's last run was a successful rj_scan_records
   rejit_amd::DeviceBuffer rec_summary, rec_counts, rec_granules;
+  // rj_scan_records_pack (record_pack.hip) shares the summary, its pinned copy and the look-back words (scratch every call
+  // writes anew) and leaves the rest of the join's state alone; rec_pack_begin: the new begins when the caller kept none
+  rejit_amd::DeviceBuffer rec_pack_begin;
   unsigned long long* rec_host = nullptr;
   const uint32_t* rec_select_counts = nullptr;
   uint64_t rec_n = 0;

@@ -42,6 +42,18 @@ def pack_records(texts: Sequence[bytes], sep: int, device, lead: int = 0, gap: i
     return text, torch.from_numpy(begins).to(device), torch.from_numpy(begins + sizes).to(device)
 
 
+def offsets_records(offsets):
+    """(rec_begin, rec_end) of an Arrow-style offsets tensor (k + 1 ascending offsets of k strings that touch): views of it
+    when it is a contiguous int64 tensor (rec_begin = offsets[:-1], rec_end = offsets[1:]), else of an int64 copy (Arrow's
+    default offsets are int32).  The records touch, so a match can run from one string into the next: Scan.pack_records
+    with the program's separator makes them independent."""
+    import torch
+
+    assert offsets.dim() == 1 and offsets.numel() >= 1
+    o = offsets.to(torch.int64).contiguous()
+    return o[:-1], o[1:]
+
+
 def relative_spans(spans, result, rec_begin, i: int):
     """Record i's matches relative to its begin: an (count, 2) int64 tensor -- spans = the scan's spans_tensor after
     run_records, result = what run_records returned."""

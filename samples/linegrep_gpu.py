@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] -- count or number the lines of FILE in which a match of PATTERN begins, the
-way `grep -E -c` / `grep -E -n | cut -d: -f1` do, with everything between the upload and the answer on the GPU:
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] -- count, number or print the lines of FILE in which a match of PATTERN
+begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
+answer on the GPU:
 
     the file is uploaded once; `^` over it is the line table (rejit_amd/records.py: line_records), PATTERN over it the match
     list, rj_scan_records joins the two on the device and rj_scan_records_select lists the lines -- only the four-word
-    summary (-c) or the selected line numbers (-n) come back.
+    summary (-c) or the selected line numbers (-n) come back.  -p: rj_scan_records_pack gathers the selected lines, a line
+    break behind each, into one new device text -- the program's output, and the only download.
 
   -c   print the number of selected lines (the default)
   -n   print their 1-based numbers, one per line
+  -p   print the selected lines themselves (grep's default output)
   -v   select the lines WITHOUT a match
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
@@ -21,13 +24,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 
 def main(argv):
-    flags = [a for a in argv if a in ("-c", "-v", "-n")]
-    rest = [a for a in argv if a not in ("-c", "-v", "-n")]
+    flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
+    rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
     if len(rest) != 2:
         sys.stderr.write(__doc__)
         return 2
     path, pattern = rest
     invert, numbers = "-v" in flags, "-n" in flags and "-c" not in flags
+    lines_out = "-p" in flags and "-c" not in flags and not numbers
     import numpy as np
     import torch
 
@@ -40,7 +44,7 @@ def main(argv):
     rejit_amd.build()
     data = np.fromfile(path, dtype=np.uint8)
     if data.size == 0:
-        if not numbers:
+        if not numbers and not lines_out:
             print(0)
         return 1
     text = torch.from_numpy(data).to("cuda:0")                       # the only upload
@@ -53,6 +57,12 @@ def main(argv):
     if numbers:
         lines = scan.select_records(invert=invert)                   # the only download besides the summary
         sys.stdout.write("".join("%d\n" % (i + 1) for i in lines.cpu().tolist()))
+    elif lines_out:
+        if selected:
+            lines = scan.select_records(invert=invert)
+            packed, _, _ = scan.pack_records(text, begins, ends, indices=lines, fill=10, lead=0, gap=1)
+            sys.stdout.flush()
+            sys.stdout.buffer.write(packed.cpu().numpy().tobytes())   # the only download besides the summary
     else:
         print(selected)
     return 0 if selected else 1
