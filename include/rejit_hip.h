@@ -255,6 +255,33 @@ int64_t rj_scan_records_pack(rj_scan* scan, const void* d_text, uint64_t n, cons
                              const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
                              int fill, uint64_t lead, uint64_t gap, void* d_out, uint64_t out_cap, uint64_t* d_out_begin,
                              uint64_t* d_out_end, void* hip_stream);
+/* The pack above in which every packed record has its OWN matches replaced by `with` (rejit_amd/csrc/record_replace.hip,
+ * DESIGN.md section 4.15): `sed 's/RE/with/g'` over lines, `str.replace` over a column, with the new record table, in one call
+ * and without a download.  k, r(j), lead, gap, fill, d_indices, out_cap, the size query and the tables are exactly those of
+ * rj_scan_records_pack.  The match list is the list of the scan's last run (rj_scan_device_spans, m = its count); d_counts /
+ * d_first are what rj_scan_records wrote for THIS record table on that run: record r's matches are spans[first[r] .. first[r] +
+ * count[r]).  R(r) = the bytes of text[rec_begin[r], rec_end[r]) with each of those matches replaced by `with` (host bytes), left
+ * to right -- what the reference's rejit::Replace (src/rejit.cc:97-112) gives on the record alone with the record-relative spans;
+ * an empty match inserts `with` at its position.  With len'(j) = len(j) - (bytes of r(j)'s matches) + count[r(j)] * with_len:
+ *     ob(0) = lead, ob(j + 1) = ob(j) + len'(j) + gap, total = ob(k)
+ *     d_out[ob(j), ob(j) + len'(j)) = R(r(j)); every other byte of d_out[0, total) = fill
+ *     d_out_begin[j] = ob(j), d_out_end[j] = ob(j) + len'(j)
+ * Bytes of a record inside a match that belongs to another record or to a gap are copied as text: only the record's own matches
+ * are replaced.  Returns total WHATEVER out_cap is, never writes at or beyond out_cap; with total <= out_cap every byte of
+ * [0, total) and every table row is written exactly once.  The scan lends scratch only: spans, stats and the state of its last
+ * rj_scan_records (rj_scan_records_select included) stay as they were.
+ * Refusals (RJ_BAD_ARGUMENT; one that names a row gives the first bad j as "row <j> "; a refused call copies nothing and is never
+ * led outside the text, the list or the output): a bad index or row, by the pack's rules; first[r] + count[r] > m; count[r] ==
+ * UINT32_MAX (saturated: the range is unknown); the row's first match begins before rec_begin[r]; the row's last match ends
+ * beyond rec_end[r] -- a crossing match: the records are not independent, rj_scan_records_pack with the separator makes them so
+ * (the list is an ordered non-overlapping selection, so the first begin and the last end bound every match of the row);
+ * d_counts or d_first NULL while k > 0; with == NULL with with_len > 0; a last run that left no list (counts-only); the
+ * argument refusals of the pack; n + (m + 1) * with_len + gap >= 2^42, or lead + k * that >= 2^62 (and k >= 2^60). */
+int64_t rj_scan_records_replace(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                                const uint64_t* d_rec_end, uint64_t n_records, const uint32_t* d_counts, const uint64_t* d_first,
+                                const uint64_t* d_indices, uint64_t n_indices, const char* with, uint64_t with_len, int fill,
+                                uint64_t lead, uint64_t gap, void* d_out, uint64_t out_cap, uint64_t* d_out_begin,
+                                uint64_t* d_out_end, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_text.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -195,7 +195,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace"]
 
 
 def load_library():
@@ -299,6 +299,8 @@ def load_library():
     L.rj_scan_records_select.argtypes = [vp, ctypes.c_int, vp, u64, vp]
     L.rj_scan_records_pack.restype = i64
     L.rj_scan_records_pack.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
+    L.rj_scan_records_replace.restype = i64
+    L.rj_scan_records_replace.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, cp, u64, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
     _lib = L
     return L
 
@@ -657,6 +659,57 @@ class Scan:
         total = call(out, int(out.numel()))
         if total > out.numel():
             raise RejitError(-4, "pack_records: the packed text has %d bytes, `out` %d" % (total, out.numel()))
+        return out[:total], out_begin, out_end
+
+    def replace_records(self, text_tensor, rec_begin, rec_end, result: RecordsResult, repl: bytes, indices=None, fill=None, lead: int = 0,
+                        gap: int = 1, out=None, stream=None):
+        """rj_scan_records_replace: pack_records in which every packed record has its own matches replaced by `repl` (bytes) --
+        `sed 's/RE/repl/g'` over lines, str.replace over a column.  `result` is the RecordsResult of the run_records that
+        produced the scan's current list (its counts and first are passed down); indices, fill, lead, gap, out and the
+        returned (out_text, out_begin, out_end) are pack_records'.  Without `out` the call makes ONE size query (table and plan
+        only) and allocates exactly `total` bytes.  RejitError (RJ_BAD_ARGUMENT, naming the first bad row) when a packed record
+        has a match that ends beyond it (the records are not independent: pack_records with the separator first), when
+        `result` is not of the scan's last run, or when that run was counts-only."""
+        import torch
+
+        t = text_tensor
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        n_records = int(rec_begin.numel())
+        for x in (rec_begin, rec_end, result.first):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
+        assert result.counts.dtype == torch.int32 and result.counts.is_contiguous() and result.counts.device == t.device and result.counts.numel() == n_records
+        repl = bytes(repl)
+        if fill is None:
+            fill = self.program.batch_separator()
+            if fill < 0:
+                raise RejitError(-4, "replace_records: the pattern has no batch separator (it is matched text by text): pass fill")
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
+        else:
+            k = n_records
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        out_begin = torch.empty(k, dtype=torch.int64, device=t.device)
+        out_end = torch.empty(k, dtype=torch.int64, device=t.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+
+        def call(buf, cap):
+            return int(_check(self._lib.rj_scan_records_replace(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records,
+                                                                ptr(result.counts), ptr(result.first), ptr(indices), k, repl, len(repl), int(fill),
+                                                                int(lead), int(gap), ptr(buf) if cap else None, cap, ptr(out_begin), ptr(out_end),
+                                                                ctypes.c_void_p(st))))
+        if out is None:
+            total = call(None, 0)
+            out = torch.empty(total, dtype=torch.uint8, device=t.device)
+            if total:
+                call(out, total)
+            return out, out_begin, out_end
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == t.device
+        total = call(out, int(out.numel()))
+        if total > out.numel():
+            raise RejitError(-4, "replace_records: the new text has %d bytes, `out` %d" % (total, out.numel()))
         return out[:total], out_begin, out_end
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:

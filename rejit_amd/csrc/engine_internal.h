@@ -171,6 +171,8 @@ struct rj_scan {
   // rj_scan_records_pack (record_pack.hip) shares the summary, its pinned copy and the look-back words (scratch every call
   // writes anew) and leaves the rest of the join's state alone; rec_pack_begin: the new begins when the caller kept none
   rejit_amd::DeviceBuffer rec_pack_begin;
+  // rj_scan_records_replace (record_replace.hip) shares all of that and with_buf; rec_repl_table: its per-match table D
+  rejit_amd::DeviceBuffer rec_repl_table;
   unsigned long long* rec_host = nullptr;
   const uint32_t* rec_select_counts = nullptr;
   uint64_t rec_n = 0;

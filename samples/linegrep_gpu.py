@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -12,6 +12,8 @@ answer on the GPU:
   -n   print their 1-based numbers, one per line
   -p   print the selected lines themselves (grep's default output)
   -v   select the lines WITHOUT a match
+  -s WITH   print every line -- with -p / -v: every selected line -- with its matches replaced by WITH (rj_scan_records_replace:
+       the new text is made on the device and is the only download): `sed -E 's/PATTERN/WITH/g'`, respectively `grep ... | sed ...`
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -24,6 +26,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 
 def main(argv):
+    repl = None
+    if "-s" in argv[:-1]:
+        at = argv.index("-s")
+        repl, argv = os.fsencode(argv[at + 1]), argv[:at] + argv[at + 2:]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
     if len(rest) != 2:
@@ -44,7 +50,7 @@ def main(argv):
     rejit_amd.build()
     data = np.fromfile(path, dtype=np.uint8)
     if data.size == 0:
-        if not numbers and not lines_out:
+        if not numbers and not lines_out and repl is None:
             print(0)
         return 1
     text = torch.from_numpy(data).to("cuda:0")                       # the only upload
@@ -54,6 +60,16 @@ def main(argv):
     scan = rejit_amd.Scan(rejit_amd.Program(pattern))
     result = scan.run_records(text, begins, ends)
     selected = result.n_records - result.n_matching if invert else result.n_matching
+    if repl is not None:
+        every = not invert and "-p" not in flags
+        lines = None if every else scan.select_records(invert=invert)
+        if every or selected:
+            new, _, _ = scan.replace_records(text, begins, ends, result, repl, indices=lines, fill=10, lead=0, gap=1)
+            if every and data[-1] not in (10, 13):                   # (sed adds no line break to a last line without one)
+                new = new[:-1]
+            sys.stdout.flush()
+            sys.stdout.buffer.write(new.cpu().numpy().tobytes())     # the only download besides the summary
+        return 0 if every or selected else 1
     if numbers:
         lines = scan.select_records(invert=invert)                   # the only download besides the summary
         sys.stdout.write("".join("%d\n" % (i + 1) for i in lines.cpu().tolist()))
