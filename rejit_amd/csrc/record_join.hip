@@ -14,36 +14,22 @@
 // 4 to 12 written; one more 8-byte read per record WITH a match (the end of its last match: does it cross).  The text is
 // not touched.
 //
-// Selection: one pass, the final place of a tile's indices from the decoupled look-back of tile_lookback.h (tickets in
-// arrival order, as emit_scan.hip): no sort, no device-wide slot counter.  A unit publishes its count BEFORE it looks
-// back, so every word it waits for belongs to a workgroup that has started and will publish without waiting.
+// Selection: one pass, the final place of a tile's indices from the decoupled look-back of tile_lookback.h through
+// record_frame.h's unit_take / unit_place (tickets in arrival order; a unit publishes its count BEFORE it looks back): no
+// sort, no device-wide slot counter.
 #include <hip/hip_runtime.h>
 
 #include "engine_internal.h"
+#include "record_frame.h"
 #include "record_join.h"
-#include "tile_lookback.h"
-#include "wave_ops.h"
 
 namespace rejit_amd {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
 constexpr uint32_t kStageBegins = 4096;   // begins a tile stages: 32 KiB of LDS, four to five workgroups per CU
 constexpr int kSelectRows = 8;            // selection: rows of 256 records per unit of the look-back
 constexpr uint64_t kSelectUnit = static_cast<uint64_t>(kSelectRows) * kThreads;
-
-// the summary both kernels write (device words, copied to the scan's pinned copy)
-enum { kSumKept = 0, kSumMatching, kSumCrossing, kSumBadRow /* ~(first bad row), 0: none */, kSumSelected, kSumTimedOut, kSumWords = 8 };
-
-// a 64-bit sum over the wave from wave_ops.h's 32-bit one: three pieces of at most 22 bits (64 x 2^22 fits easily)
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
-  const uint64_t a = wave_total(static_cast<uint32_t>(x) & 0x3FFFFFu);
-  const uint64_t b = wave_total(static_cast<uint32_t>(x >> 22) & 0x3FFFFFu);
-  const uint64_t c = wave_total(static_cast<uint32_t>(x >> 44));
-  return a + (b << 22) + (c << 44);
-}
 
 __global__ __launch_bounds__(kThreads) void record_join_kernel(const uint64_t* __restrict__ spans, uint64_t m, const uint64_t* __restrict__ rec_begin,
                                                                const uint64_t* __restrict__ rec_end, uint64_t n_records, uint64_t n,
@@ -106,14 +92,14 @@ __global__ __launch_bounds__(kThreads) void record_join_kernel(const uint64_t* _
     s_part[wv][kSumKept] = acc_kept;
     s_part[wv][kSumMatching] = acc_matching;
     s_part[wv][kSumCrossing] = acc_crossing;
-    s_part[wv][kSumBadRow] = ~acc_bad;   // (the largest complement is the smallest row; 0: none)
+    s_part[wv][kSumBadWord] = ~acc_bad;   // (the largest complement is the smallest row; 0: none)
   }
   __syncthreads();
   if (tid < 4) {
     unsigned long long v = 0;
-    for (int w = 0; w < kWaves; w++) v = tid == kSumBadRow ? (s_part[w][tid] > v ? s_part[w][tid] : v) : v + s_part[w][tid];
+    for (int w = 0; w < kWaves; w++) v = tid == kSumBadWord ? (s_part[w][tid] > v ? s_part[w][tid] : v) : v + s_part[w][tid];
     if (v != 0) {
-      if (tid == kSumBadRow) atomicMax(&summary[tid], v);
+      if (tid == kSumBadWord) atomicMax(&summary[tid], v);
       else atomicAdd(&summary[tid], v);
     }
   }
@@ -125,18 +111,13 @@ __global__ __launch_bounds__(kThreads) void record_join_kernel(const uint64_t* _
 __global__ __launch_bounds__(kThreads) void record_select_kernel(const uint32_t* __restrict__ counts, uint64_t n_records, int invert,
                                                                  unsigned long long* granules, unsigned long long* ticket, uint64_t n_units,
                                                                  uint64_t* __restrict__ out, uint64_t cap, unsigned long long* summary) {
-  __shared__ unsigned long long s_ticket, s_before;
+  __shared__ UnitPlace s_unit;
   __shared__ uint32_t s_count[kSelectRows][kWaves];
-  __shared__ uint32_t s_timed_out;
   const uint32_t tid = threadIdx.x;
   const int wv = static_cast<int>(tid) >> 6;
   const int lane = lane_id();
-  if (tid == 0) s_timed_out = 0;
-  for (;;) {
-    if (tid == 0) s_ticket = atomicAdd(ticket, 1ull);
-    __syncthreads();
-    const uint64_t tk = s_ticket;
-    if (tk >= n_units) return;
+  unit_init(s_unit);
+  for (uint64_t tk; unit_take(s_unit, ticket, n_units, &tk);) {
     const uint64_t base = tk * kSelectUnit;
     uint64_t mask[kSelectRows];
 #pragma unroll
@@ -147,24 +128,10 @@ __global__ __launch_bounds__(kThreads) void record_select_kernel(const uint32_t*
       if (lane == 0) s_count[j][wv] = static_cast<uint32_t>(__popcll(mask[j]));
     }
     __syncthreads();
-    if (wv == 0) {
-      const uint32_t total = wave_total(lane < kSelectRows * kWaves ? s_count[lane / kWaves][lane % kWaves] : 0u);
-      if (lane == 0) lookback::publish(granules, n_units, tk, total);
-      unsigned long long before = 0;
-      const bool ok = lookback::resolve(granules, n_units, tk, &before);
-      if (lane == 0) {
-        s_before = before;
-        if (!ok) {
-          s_timed_out = 1;
-          summary[kSumTimedOut] = 1;
-        } else if (tk == n_units - 1) {
-          summary[kSumSelected] = before + total;
-        }
-      }
-    }
-    __syncthreads();
-    if (s_timed_out == 0) {
-      uint64_t at = s_before;
+    const uint32_t total = wv == 0 ? wave_total(lane < kSelectRows * kWaves ? s_count[lane / kWaves][lane % kWaves] : 0u) : 0u;
+    if (unit_place(s_unit, total, tk, n_units, granules, summary)) {
+      if (tk == n_units - 1 && tid == 0) summary[kSumSelected] = s_unit.end;
+      uint64_t at = s_unit.before;
 #pragma unroll
       for (int j = 0; j < kSelectRows; j++) {
         uint32_t waves_before = 0, row = 0;
@@ -182,12 +149,6 @@ __global__ __launch_bounds__(kThreads) void record_select_kernel(const uint32_t*
       }
     }
   }
-}
-
-int ensure_summary(rj_scan* s) {
-  if (!s->rec_host) RJ_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->rec_host), kSumWords * sizeof(unsigned long long)));
-  RJ_HIP(s->rec_summary.reserve(kSumWords * sizeof(unsigned long long)));
-  return RJ_OK;
 }
 
 }  // namespace
@@ -211,25 +172,21 @@ int64_t rj_scan_records(rj_scan* s, const void* d_text, uint64_t n, const uint64
   rj_record_stats out{};
   out.n_matches = m;
   if (n_records) {
-    rc = ensure_summary(s);
-    if (rc != RJ_OK) return rc;
     uint32_t* counts = d_counts;
     if (!counts) {
       RJ_HIP(s->rec_counts.reserve(n_records * sizeof(uint32_t)));
       counts = s->rec_counts.as<uint32_t>();
     }
-    unsigned long long* summary = s->rec_summary.as<unsigned long long>();
-    RJ_HIP(hipMemsetAsync(summary, 0, kSumWords * sizeof(unsigned long long), st));
+    unsigned long long *scratch = nullptr, *summary = nullptr;
+    if ((rc = records_begin(s, 0, st, &scratch, &summary)) != RJ_OK) return rc;
     const uint64_t n_tiles = (n_records + kThreads - 1) / kThreads;
     const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(n_tiles, 1u << 20));   // (more tiles: a workgroup takes several)
     hipLaunchKernelGGL(record_join_kernel, dim3(grid), dim3(kThreads), 0, st, s->result, m, d_rec_begin, d_rec_end, n_records, n, kStageBegins,
                        counts, d_first, summary);
-    RJ_HIP(hipMemcpyAsync(s->rec_host, summary, kSumWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    RJ_HIP(hipStreamSynchronize(st));
-    RJ_HIP(hipGetLastError());
-    if (s->rec_host[kSumBadRow] != 0)
+    if ((rc = records_finish(s, "rj_scan_records", st)) != RJ_OK) return rc;
+    if (s->rec_host[kSumBadWord] != 0)
       return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records: row %llu of the record table is not ascending or not inside the text (begin <= end <= next begin, end <= n)",
-                     static_cast<unsigned long long>(~s->rec_host[kSumBadRow]));
+                     static_cast<unsigned long long>(~s->rec_host[kSumBadWord]));
     out.n_kept = s->rec_host[kSumKept];
     out.n_matching = s->rec_host[kSumMatching];
     out.n_crossing = s->rec_host[kSumCrossing];
@@ -248,22 +205,13 @@ int64_t rj_scan_records_select(rj_scan* s, int invert, uint64_t* d_indices, uint
   if (cap && !d_indices) return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records_select: null argument");
   if (s->rec_n == 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  int rc = ensure_summary(s);
-  if (rc != RJ_OK) return rc;
   const uint64_t n_units = (s->rec_n + kSelectUnit - 1) / kSelectUnit;
-  const size_t scratch_bytes = (lookback::granule_words(n_units) + 1) * sizeof(unsigned long long);   // the ticket, then the look-back's words
-  RJ_HIP(s->rec_granules.reserve(scratch_bytes));
-  unsigned long long* scratch = s->rec_granules.as<unsigned long long>();
-  unsigned long long* summary = s->rec_summary.as<unsigned long long>();
-  RJ_HIP(hipMemsetAsync(scratch, 0, scratch_bytes, st));
-  RJ_HIP(hipMemsetAsync(summary, 0, kSumWords * sizeof(unsigned long long), st));
-  const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(n_units, 1024));   // persistent: workgroups take units until none is left
-  hipLaunchKernelGGL(record_select_kernel, dim3(grid), dim3(kThreads), 0, st, s->rec_select_counts, s->rec_n, invert, scratch + 1, scratch, n_units,
-                     d_indices, cap, summary);
-  RJ_HIP(hipMemcpyAsync(s->rec_host, summary, kSumWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  RJ_HIP(hipStreamSynchronize(st));
-  RJ_HIP(hipGetLastError());
-  if (s->rec_host[kSumTimedOut] != 0) return rj_fail(RJ_DEVICE_ERROR, "rj_scan_records_select: the look-back timed out");
+  unsigned long long *scratch = nullptr, *summary = nullptr;   // scratch: the ticket, then the look-back's words
+  int rc = records_begin(s, 1 + lookback::granule_words(n_units), st, &scratch, &summary);
+  if (rc != RJ_OK) return rc;
+  hipLaunchKernelGGL(record_select_kernel, dim3(unit_grid(n_units)), dim3(kThreads), 0, st, s->rec_select_counts, s->rec_n, invert, scratch + 1, scratch,
+                     n_units, d_indices, cap, summary);
+  if ((rc = records_finish(s, "rj_scan_records_select", st)) != RJ_OK) return rc;
   return static_cast<int64_t>(s->rec_host[kSumSelected]);
 }
 

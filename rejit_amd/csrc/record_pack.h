@@ -93,28 +93,45 @@ RJ_PACK_HD inline uint64_t chunk_end_row(const View& table, uint64_t k, uint64_t
 // rows a chunk stages: ob of [j0, j1] (the row behind the last one bounds it), the source begins of [j0, j1)
 RJ_PACK_HD inline bool chunk_fits_stage(const Rows& r, uint64_t stage_cap) { return r.j1 - r.j0 < stage_cap; }
 
+// The row around output byte p: out[ob, data_end) = the row's bytes, out[data_end, next) = fill.  Before the first row -- the
+// lead, or an output without rows -- everything is fill and `row` is not called; else row(j) fetches what the caller keeps of
+// row j besides its place (replace::locate_row builds on this one too).
+struct RowAt {
+  uint64_t ob, data_end, next;
+};
+template <class RowFn>
+RJ_PACK_HD inline RowAt locate_row(const View& v, const Rows& r, uint64_t p, uint64_t gap, const RowFn& row) {
+  const uint64_t u = upper_bound(v, r.j0, r.j1, p);
+  RowAt at;
+  if (u == r.j0) {
+    at.ob = at.data_end = p;
+    at.next = v.ob_at(r.j0);
+    return at;
+  }
+  const uint64_t j = u - 1;
+  at.ob = v.ob_at(j);
+  at.next = v.ob_at(j + 1);
+  at.data_end = at.next - gap;
+  row(j);
+  return at;
+}
+
 // The piece of the output around byte p: out[ob, data_end) = text[src + (p - ob)], out[data_end, next) = fill.
 struct Piece {
   uint64_t ob, data_end, next, src;
 };
 RJ_PACK_HD inline Piece locate(const View& v, const Rows& r, uint64_t p, uint64_t gap) {
-  const uint64_t u = upper_bound(v, r.j0, r.j1, p);
-  Piece pc;
-  if (u == r.j0) {   // before the first row: the lead (or an output without rows)
-    pc.ob = pc.data_end = p;
-    pc.next = v.ob_at(r.j0);
-    pc.src = 0;
-    return pc;
-  }
-  const uint64_t j = u - 1;
-  pc.ob = v.ob_at(j);
-  pc.next = v.ob_at(j + 1);
-  pc.data_end = pc.next - gap;
-  pc.src = v.src_at(j);
-  return pc;
+  uint64_t src = 0;
+  const RowAt at = locate_row(v, r, p, gap, [&](uint64_t j) { src = v.src_at(j); });
+  return Piece{at.ob, at.data_end, at.next, src};
 }
 
 RJ_PACK_HD inline uint32_t fill_word(uint32_t fill) { return fill * 0x01010101u; }
+// byte b of the 16 in w becomes c
+RJ_PACK_HD inline void put_byte(uint32_t w[4], uint32_t b, uint32_t c) {
+  const uint32_t sh = 8 * (b & 3);
+  w[b >> 2] = (w[b >> 2] & ~(0xFFu << sh)) | (c << sh);
+}
 
 // The 16 output bytes [p, p + 16), p a multiple of 16, of which those below `limit` (= min(total, out_cap)) matter: four
 // little-endian words.  Text::load16(s, w) reads text[s, s + 16) -- all of it inside one record --, Text::byte(s) one byte.
@@ -135,11 +152,7 @@ RJ_PACK_HD inline int group16(const View& v, const Rows& r, uint64_t p, uint64_t
     const uint64_t q = p + b;
     if (q >= limit) break;
     if (q >= pc.next) pc = locate(v, r, q, gap);
-    if (q < pc.data_end) {
-      const uint32_t c = text.byte(pc.src + (q - pc.ob));
-      const uint32_t sh = 8 * (b & 3);
-      w[b >> 2] = (w[b >> 2] & ~(0xFFu << sh)) | (c << sh);
-    }
+    if (q < pc.data_end) put_byte(w, b, text.byte(pc.src + (q - pc.ob)));
   }
   return 2;
 }

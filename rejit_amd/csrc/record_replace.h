@@ -124,24 +124,15 @@ struct Row {
 };
 template <class Mem>
 RJ_PACK_HD inline Row locate_row(const pack::View& v, const Stage& st, const Mem& M, bool have_indices, const pack::Rows& r, uint64_t p, uint64_t gap) {
-  const uint64_t u = pack::upper_bound(v, r.j0, r.j1, p);
-  Row row;
-  if (u == r.j0) {   // before the first row: the lead (or an output without rows)
-    row.ob = row.data_end = p;
-    row.next = v.ob_at(r.j0);
-    row.x = RowInfo{0, 0, 0, 0};
-    return row;
-  }
-  const uint64_t j = u - 1;
-  row.ob = v.ob_at(j);
-  row.next = v.ob_at(j + 1);
-  row.data_end = row.next - gap;
-  if (st.first) {
-    row.x = RowInfo{v.src[j - v.base], st.first[j - v.base], st.base[j - v.base], st.count[j - v.base]};
-  } else {
-    row.x = row_info(M, j, have_indices);
-  }
-  return row;
+  RowInfo x{0, 0, 0, 0};
+  const pack::RowAt at = pack::locate_row(v, r, p, gap, [&](uint64_t j) {
+    if (st.first) {
+      x = RowInfo{v.src[j - v.base], st.first[j - v.base], st.base[j - v.base], st.count[j - v.base]};
+    } else {
+      x = row_info(M, j, have_indices);
+    }
+  });
+  return Row{at.ob, at.data_end, at.next, x};
 }
 
 // The piece of the row around output byte p (ob <= p < next): out[begin, end) is text[src, ...), with[0, W) or fill.
@@ -193,11 +184,7 @@ RJ_PACK_HD inline int group16(const pack::View& v, const Stage& st, const Mem& M
       if (q >= row.next) row = locate_row(v, st, M, have_indices, r, q, gap);
       pc = locate_piece(M, row, q, with_len);
     }
-    if (pc.kind != kFill) {
-      const uint32_t c = pc.kind == kText ? text.byte(pc.src + (q - pc.begin)) : M.with_byte(q - pc.begin);
-      const uint32_t sh = 8 * (b & 3);
-      w[b >> 2] = (w[b >> 2] & ~(0xFFu << sh)) | (c << sh);
-    }
+    if (pc.kind != kFill) pack::put_byte(w, b, pc.kind == kText ? text.byte(pc.src + (q - pc.begin)) : M.with_byte(q - pc.begin));
   }
   return 2;
 }

@@ -12,37 +12,9 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_pack.h"
+#include "checked_text.h"
 
 using namespace rejit_amd::pack;
-
-namespace {
-
-inline uint8_t synth(uint64_t s) { return static_cast<uint8_t>((s * 131u + (s >> 8) * 7u + (s >> 32)) & 0xFFu); }
-
-struct CheckedText {
-  const uint8_t* text;
-  uint64_t n;
-  mutable bool left_range = false;
-  mutable uint64_t loads16 = 0, byte_reads = 0;
-  uint32_t at(uint64_t s) const {
-    if (s >= n) {
-      left_range = true;
-      return 0;
-    }
-    return text ? text[s] : synth(s);
-  }
-  void load16(uint64_t s, uint32_t w[4]) const {
-    loads16++;
-    for (int i = 0; i < 4; i++) w[i] = 0;
-    for (uint32_t b = 0; b < 16; b++) w[b >> 2] |= at(s + b) << (8 * (b & 3));
-  }
-  uint32_t byte(uint64_t s) const {
-    byte_reads++;
-    return at(s);
-  }
-};
-
-}  // namespace
 
 // summary: [0] total, [1] first bad row (~0: none), [2] chunks that used the stage, [3] chunks that searched the table,
 // [4] groups that were one load16, [5] groups of fill only, [6] groups that went byte by byte, [7] single bytes read.
@@ -112,9 +84,7 @@ extern "C" long pe_pack(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
       uint32_t w[4];
       const int how = group16(view, rows, p, limit, gap, fill, src, w);
       summary[4 + how]++;
-      const uint32_t bytes = group_store_bytes(p, limit);
-      if (bytes == 0 || bytes > kGroupBytes || p + bytes > out_cap) return -1;
-      for (uint32_t b = 0; b < bytes; b++) out[p - window0 + b] = static_cast<uint8_t>(w[b >> 2] >> (8 * (b & 3)));
+      if (!store_group(out, window0, p, limit, out_cap, w)) return -1;
     }
   }
   summary[7] = src.byte_reads;

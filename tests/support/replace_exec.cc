@@ -12,32 +12,11 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_replace.h"
+#include "checked_text.h"
 
 using namespace rejit_amd;
 
 namespace {
-
-struct CheckedText {
-  const uint8_t* text;
-  uint64_t n;
-  mutable bool left_range = false;
-  mutable uint64_t byte_reads = 0;
-  uint32_t at(uint64_t s) const {
-    if (s >= n) {
-      left_range = true;
-      return 0;
-    }
-    return text[s];
-  }
-  void load16(uint64_t s, uint32_t w[4]) const {
-    for (int i = 0; i < 4; i++) w[i] = 0;
-    for (uint32_t b = 0; b < 16; b++) w[b >> 2] |= at(s + b) << (8 * (b & 3));
-  }
-  uint32_t byte(uint64_t s) const {
-    byte_reads++;
-    return at(s);
-  }
-};
 
 struct CheckedMem {
   const uint64_t *rb, *re, *first_;
@@ -157,9 +136,7 @@ extern "C" long re_replace(const uint8_t* text, uint64_t n, const uint64_t* rec_
       uint32_t w[4];
       const int how = replace::group16(view, stage, M, have_indices != 0, rows, p, limit, gap, fill, with_len, src, w);
       summary[5 + how]++;
-      const uint32_t bytes = pack::group_store_bytes(p, limit);
-      if (bytes == 0 || bytes > replace::kGroupBytes || p + bytes > out_cap) return -1;
-      for (uint32_t b = 0; b < bytes; b++) out[p + b] = static_cast<uint8_t>(w[b >> 2] >> (8 * (b & 3)));
+      if (!store_group(out, 0, p, limit, out_cap, w)) return -1;
     }
   }
   return src.left_range || M.left_range ? -1 : 0;

@@ -185,6 +185,48 @@ def test_no_rows_and_empty_outputs(rj, scan):
     assert out.numel() == 0 and ob.numel() == 0 and oe.numel() == 0
 
 
+@pytest.mark.parametrize("k", [1, 257, 64 * 256 + 1])
+def test_without_a_match_the_replace_is_the_pack(rj, scan, k):
+    """A pattern that matches nowhere in the text: replace_records is pack_records, byte for byte and row for row -- the two
+    policies of the one copy kernel frame (record_frame.h's copy_chunks) describe the same output.  One row, 257 rows and one
+    look-back group plus one unit; lead 3, gap 1; out_cap whole and cutting a record."""
+    import torch
+    lib = rj.load_library()
+    rng = np.random.RandomState(k)
+    lens = rng.choice([0, 1, 15, 16, 17, 40, 100], k)
+    cut_row = k // 2
+    lens[cut_row] = 40
+    rb = 5 + np.concatenate([[0], np.cumsum(lens + rng.randint(0, 3, k))[:-1]]).astype(np.int64)
+    re_ = rb + lens
+    t = letters(int(re_[-1]) + 9, k)
+    data, n = t.tobytes(), len(t)
+    d = torch.from_numpy(t).to("cuda:0")
+    rb_t, re_t = dev(rb), dev(re_)
+    res = scan.run_records(d, rb_t, re_t)
+    assert res.n_matches == 0 and res.n_kept == 0
+    want, w_ob, w_oe = expect([[data[b:e]] for b, e in zip(rb.tolist(), re_.tolist())], range(k), b"xyz", 0x7C, 3, 1)
+    want = np.frombuffer(want, dtype=np.uint8)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    vp = lambda x: ctypes.c_void_p(x.data_ptr())
+    for cap in (int(w_ob[cut_row]) + 20, len(want)):
+        got = []
+        for replace in (False, True):
+            buf = torch.full((len(want) + 64,), POISON, dtype=torch.uint8, device="cuda:0")
+            ob = torch.full((k,), -7, dtype=torch.int64, device="cuda:0")
+            oe = torch.full((k,), -7, dtype=torch.int64, device="cuda:0")
+            if replace:
+                total = lib.rj_scan_records_replace(scan._h, vp(d), n, vp(rb_t), vp(re_t), k, vp(res.counts), vp(res.first), None, 0, b"xyz", 3, 0x7C, 3, 1,
+                                                    vp(buf), cap, vp(ob), vp(oe), st)
+            else:
+                total = lib.rj_scan_records_pack(scan._h, vp(d), n, vp(rb_t), vp(re_t), k, None, 0, 0x7C, 3, 1, vp(buf), cap, vp(ob), vp(oe), st)
+            assert total == len(want), (k, cap, replace, total)
+            got.append((buf.cpu().numpy(), ob.cpu().numpy(), oe.cpu().numpy()))
+        (p_out, p_ob, p_oe), (r_out, r_ob, r_oe) = got
+        assert (r_out == p_out).all() and (r_ob == p_ob).all() and (r_oe == p_oe).all(), (k, cap)
+        assert (p_out[:cap] == want[:cap]).all() and (p_out[cap:] == POISON).all(), (k, cap)
+        assert (p_ob == w_ob).all() and (p_oe == w_oe).all(), (k, cap)
+
+
 # ------------------------------------------------------------------------------------------------ skew
 def test_one_record_with_a_million_matches_and_a_million_records_with_one(rj, scan):
     """16 MiB with LIT in every block of 16 bytes: as ONE record among 50 000 empty ones, and as 2^20 records of 16 bytes.

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
 SO = os.path.join(HERE, "support", "libpack_exec.so")
 SRCS = [os.path.join(HERE, "support", "pack_exec.cc")]
-DEPS = SRCS + [os.path.join(CSRC, "record_pack.h")]
+DEPS = SRCS + [os.path.join(HERE, "support", "checked_text.h"), os.path.join(CSRC, "record_pack.h")]
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 NONE = (1 << 64) - 1

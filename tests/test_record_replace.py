@@ -17,13 +17,16 @@ import subprocess
 
 import pytest
 
+import test_record_pack as the_pack
+from test_record_pack import px  # noqa: F401  (the fixture: the pack's driver, pack_exec.cc)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
 SO = os.path.join(HERE, "support", "libreplace_exec.so")
 EXE = os.path.join(HERE, "support", "replace_exec_asan")
 SRCS = [os.path.join(HERE, "support", "replace_exec.cc")]
-DEPS = SRCS + [os.path.join(CSRC, "record_replace.h"), os.path.join(CSRC, "record_pack.h")]
+DEPS = SRCS + [os.path.join(HERE, "support", "checked_text.h"), os.path.join(CSRC, "record_replace.h"), os.path.join(CSRC, "record_pack.h")]
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -329,6 +332,45 @@ def test_refusals_name_the_first_bad_row_and_nothing_is_copied(rx, what, want, k
                 assert bad == want and got_kind == kind, (what, unit, chunk, cap)
                 if want is not None:
                     assert out == bytes([POISON]) * len(out)          # a refused call copies nothing
+
+
+def test_with_nothing_to_replace_the_replace_is_the_pack(rx, px):  # noqa: F811
+    """An empty match list (m = 0, every count 0): re_replace gives the bytes, ob / oe and the total of pe_pack through the
+    other driver -- the one fact the copy frame the two kernels share (record_frame.h's copy_chunks) relies on: the two policies
+    describe the same output when there is nothing to replace.  Units of 256, chunks of 64 bytes, a stage of 4 and 1024 rows."""
+    rng = random.Random(23)
+    seen_pack, seen_replace = [0] * 8, [0] * 8
+    for k in (0, 1, 255, 256, 257):
+        records, at = [], rng.choice([0, 3])
+        for _ in range(k):
+            size = rng.choice([0, 0, 1, 15, 16, 17, 40, 100])
+            records.append((at, at + size))
+            at += size + rng.choice([0, 0, 2])
+        text = _text(at + 5, seed=k + 1)
+        for indices in (None, [rng.randrange(k) for _ in range(k + 3)] if k else []):
+            for lead in (0, 3):
+                for gap in (0, 1):
+                    want, w_ob, w_oe = the_pack.brute(text, records, indices, lead, gap)
+                    inside = [(b + e) // 2 for b, e in zip(w_ob, w_oe) if e - b >= 2]
+                    middle = inside[len(inside) // 2] if inside else len(want) // 2
+                    for out_cap in (0, middle, len(want)):
+                        for cap in (4, 1024):
+                            ctx = (k, indices is not None, lead, gap, out_cap, cap)
+                            p_rc, p_total, p_bad, p_out, p_ob, p_oe, p_summ = the_pack.run(px, text, len(text), records, indices, lead, gap, 256, 64,
+                                                                                           cap, out_cap=out_cap)
+                            r_rc, r_total, r_bad, _, r_out, r_ob, r_oe, r_summ = run(rx, text, len(text), records, [], [0] * len(records),
+                                                                                     [0] * len(records), indices, b"xyz", lead, gap, 256, 64, cap,
+                                                                                     out_cap=out_cap)
+                            assert p_rc == 0 and r_rc == 0 and p_bad is None and r_bad is None, ctx
+                            assert r_total == p_total == len(want), ctx
+                            assert r_out == p_out and r_out[:out_cap] == want[:out_cap], ctx      # (both buffers: out_cap + 32 poisoned bytes)
+                            limit = min(out_cap, len(want))
+                            assert r_out[limit:] == bytes([POISON]) * (len(r_out) - limit), ctx            # nothing at or beyond total / out_cap
+                            assert r_ob == p_ob == w_ob and r_oe == p_oe == w_oe, ctx
+                            seen_pack = [a + b for a, b in zip(seen_pack, p_summ)]
+                            seen_replace = [a + b for a, b in zip(seen_replace, r_summ)]
+    # staged chunks and chunks that searched the tables, several chunks per call, in both drivers
+    assert seen_pack[2] and seen_pack[3] and seen_replace[3] == seen_pack[2] and seen_replace[4] == seen_pack[3], (seen_pack, seen_replace)
 
 
 def test_the_bounds_on_the_sums_at_their_edges(rx):
