@@ -22,6 +22,7 @@
 
 #include "engine_internal.h"
 #include "exact_count.h"
+#include "plane_args.h"
 
 using namespace rejit_amd;
 
@@ -286,6 +287,21 @@ PlanePlan plan_plane_general(const std::vector<rj_scan*>& scans) {
   return pl;
 }
 
+// One run of the batched pipeline or of the count kernel: its arguments, the geometry they give, and the state of the attempt
+// in flight -- what collect_* needs from enqueue_*.  rj_multi_start leaves it in rj_multi::pending for rj_multi_finish.
+struct MultiRun {
+  const uint8_t* text = nullptr;
+  uint64_t n = 0, sb = 0, se = 0;
+  hipStream_t st = nullptr;      // the caller's stream
+  bool fuse = false;             // one scan kernel for all patterns ...
+  bool plane = false;            // ... the bit-plane scan over `blocks`
+  PlaneBlocks blocks;
+  ScanGeometry geo{};
+  std::vector<uint64_t> caps;    // this attempt's region capacity per pattern,
+  uint32_t shared_cap = 0;       // of the shared candidate regions;
+  bool fused_launched = false;   // its scan kernel classified its own candidates (plane_scan_classify)
+};
+
 }  // namespace
 
 struct rj_multi {
@@ -298,13 +314,14 @@ struct rj_multi {
   bool fused_classify = true;
   bool want_fused_classify = false;  // rj_multi_set_mode(m, 4): mode 0 with the one-kernel form
   bool flags_clean = false;   // the counters that kernel may set but does not clear are zero on the device
-  bool last_was_fused_classify = false;
   // what classify_shared_multi copies into LDS: ClassifyDesc[P] + the patterns' tables (kernels.h)
   DeviceBuffer classify_blob;
   ClassifyDesc* host_desc = nullptr;   // pinned
   std::vector<ClassifyDesc> desc_uploaded;
   uint32_t desc_words = 0, blob_words = 0;
   bool classify_tables_ready = false;
+  int max_words = 1;          // the largest automaton of the set, its longest bounded match: what the classifying kernels are
+  uint32_t max_short = 0;     // instantiated for
   DeviceBuffer dummy_counts;  // hit_counts of the padding patterns
   DeviceBuffer tails;         // MultiTail[P]
   MultiTail* host_tails = nullptr;  // pinned
@@ -319,13 +336,8 @@ struct rj_multi {
   // rj_multi_start / rj_multi_finish: a run whose kernels are enqueued and whose results have not been collected
   struct Pending {
     bool active = false;
-    int kind = 0;  // rj_multi_run's return value: 1 one pass, 2 separate scans + batched tails, 0 one pipeline after the other
-    const uint8_t* text = nullptr;
-    uint64_t n = 0, sb = 0, se = 0;
-    hipStream_t st = nullptr;
-    bool fuse = false;
-    std::vector<uint64_t> caps;
-    uint32_t shared_cap = 0;
+    int kind = 0;  // rj_multi_run's return value: 3 counts, 1 one pass, 2 separate scans + batched tails, 0 one pipeline after the other
+    MultiRun run;
     hipEvent_t done = nullptr;  // behind the run's last kernel: rj_multi_finish waits for THIS run, not for the stream
   } pending;
   rj_multi* scan_after = nullptr;  // rj_multi_order_after: this object's scan kernel waits for that one's
@@ -346,86 +358,330 @@ struct rj_multi {
   PlanePlan gplane;
   bool general_counts = false;
   DeviceBuffer count_blob;
-  uint32_t count_desc_words = 0, count_blob_words = 0, count_lmax = 0, count_max_short = 0;
-  int count_max_words = 1;
+  uint32_t count_desc_words = 0, count_blob_words = 0;
   bool count_blob_ready = false;
   bool last_counts = false;    // the last run left counts (no span lists)
   uint32_t counts_fallbacks = 0;
-
 };
 
 namespace {
 
-SharedHits shared_hits_of(rj_multi* m, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, uint32_t shared_cap, uint32_t n_regions, int P) {
+int n_patterns(const rj_multi* m) { return static_cast<int>(m->scans.size()); }
+
+// ----------------------------------------------------------------------------- one builder per launch argument
+// the window positions and blocks of a plan over the starts [sb, se): the general plan's patterns have their own offsets
+PlaneBlocks blocks_of(const PlanePlan& pl, uint64_t n, uint64_t sb, uint64_t se) {
+  return pl.general ? plane_blocks(n, sb, se, pl.min_offset, pl.max_offset, pl.n_cmp) : plane_blocks(n, sb, se, pl.offset, pl.offset, 8);
+}
+
+// what plane_count, plane_list and their general forms share: the text, the blocks dealt out to n_regions waves, the plan
+PlaneCountParams plane_count_params(const rj_multi* m, const PlanePlan& pl, const MultiRun& r, uint32_t batch_at) {
+  PlaneCountParams c{};
+  c.text = r.text;
+  c.n = r.n;
+  c.sb = r.sb;
+  c.se = r.se;
+  c.first_block = r.blocks.first_block;
+  c.end_block = r.blocks.end_block;
+  plane_split(r.blocks.blocks(), r.geo.n_regions, &c.span_blocks, &c.span_extra);
+  c.code_shift = pl.code_shift;
+  c.n_bases = pl.n_bases;
+  c.n_patterns = static_cast<uint32_t>(n_patterns(m));
+  c.batch_at = batch_at;
+  return c;
+}
+
+// the shared candidate regions a list kernel writes, the counter blocks it clears: the same fields in all four structs
+template <class Params>
+void shared_regions(rj_multi* m, const MultiRun& r, Params* a) {
+  a->hits = m->shared_hits.as<uint64_t>();
+  a->region_cap = r.shared_cap;
+  a->hit_counts = m->shared_counts.as<uint32_t>();
+  a->n_zero = static_cast<uint32_t>(n_patterns(m));
+  for (uint32_t p = 0; p < a->n_zero; p++) a->zero_counters[p] = m->scans[p]->counters.as<unsigned long long>();
+}
+
+PlaneParams plane_params(rj_multi* m, const MultiRun& r) {
+  const PlanePlan& pl = m->plane;
+  PlaneParams pp{};
+  pp.text = r.text;
+  pp.n = r.n;
+  pp.sb = r.sb;
+  pp.se = r.se;
+  pp.span_pairs = r.blocks.span_pairs(r.geo.n_regions);
+  pp.offset = pl.offset;
+  pp.code_shift = pl.code_shift;
+  pp.n_bases = pl.n_bases;
+  plane_masks(pl.base, pl.n_bases, pl.code_shift, 2, pp.lo, pp.hi);
+  shared_regions(m, r, &pp);
+  return pp;
+}
+
+PlaneGParams plane_g_params(rj_multi* m, const MultiRun& r) {
+  const PlanePlan& pl = m->plane;
+  PlaneGParams pg{};
+  pg.text = r.text;
+  pg.n = r.n;
+  pg.wlo = r.blocks.wlo;
+  pg.whi = r.blocks.whi;
+  pg.span_pairs = r.blocks.span_pairs(r.geo.n_regions);
+  pg.code_shift = pl.code_shift;
+  pg.n_bases = pl.n_bases;
+  pg.n_cmp = pl.n_cmp;
+  pg.tolerance = pl.tolerance;
+  plane_masks(pl.base, pl.n_bases, pl.code_shift, kPlaneMaxBases, pg.lo, pg.hi);
+  shared_regions(m, r, &pg);
+  return pg;
+}
+
+PlaneListParams plane_list_params(rj_multi* m, const MultiRun& r) {
+  const PlanePlan& pl = m->plane;
+  PlaneListParams a{};
+  a.c = plane_count_params(m, pl, r, 64);
+  a.c.mask_bits = plane_mask_bits(pl.base, pl.n_bases, pl.code_shift);
+  a.offset = pl.offset;
+  shared_regions(m, r, &a);
+  return a;
+}
+
+// (lmax, desc_words and c.table stay zero for the list kernel)
+PlaneCountGParams plane_count_g_params(const rj_multi* m, const PlanePlan& pl, const MultiRun& r, uint32_t batch_at) {
+  PlaneCountGParams g{};
+  g.c = plane_count_params(m, pl, r, batch_at);
+  g.n_cmp = pl.n_cmp;
+  g.tolerance = pl.tolerance;
+  plane_idx(pl.base, pl.n_bases, pl.code_shift, pl.n_cmp, kPlaneMaxBases, g.idx);
+  return g;
+}
+
+PlaneListGParams plane_list_g_params(rj_multi* m, const MultiRun& r) {
+  PlaneListGParams a{};
+  a.g = plane_count_g_params(m, m->plane, r, 64);
+  a.offset = 0;
+  shared_regions(m, r, &a);
+  return a;
+}
+
+// Shared prefilter (kernels.hip: fused_chunk_d1): are all windows within one nibble of <= 2 base
+// windows?  Nibbles are compared on their low 3 bits there.  A base is a window without
+// wildcards; greedy: the first uncovered exact window becomes the next base.  Returns their number, 0: no prefilter.
+int fused_prefilter_bases(const FusedParams& fp, int P, uint32_t bases[2]) {
+  auto nibbles_off = [](uint32_t v, uint32_t k, uint32_t base) {  // nibbles in which (v, k) leaves `base` free or differs
+    int d = 0;
+    for (int i = 0; i < 8; i++) {
+      const uint32_t kk = (k >> (4 * i)) & 7u, vv = (v >> (4 * i)) & 7u, bb = (base >> (4 * i)) & 7u;
+      d += (kk == 0 || vv != bb) ? 1 : 0;
+    }
+    return d;
+  };
+  int nb = 0;
+  for (int pass = 0; pass < 2; pass++)
+    for (int p = 0; p < P; p++)
+      for (int w = 0; w < 2; w++) {
+        const uint32_t v = fp.value[p][w] & 0x77777777u, k = fp.mask[p][w] & 0x77777777u;
+        bool covered = false;
+        for (int b = 0; b < nb; b++) covered = covered || nibbles_off(v, k, bases[b]) <= 1;
+        if (covered) continue;
+        if (pass == 1) return 0;  // second pass: still not within one nibble of a base
+        if (k == 0x77777777u && nb < 2) bases[nb++] = v;  // an exact window: a new base
+      }
+  return nb;
+}
+
+// scan_windows_fused: every pattern's two nibble-form windows and its own regions (after regions_for_attempt)
+FusedParams fused_params(rj_multi* m, const MultiRun& r) {
+  const int P = n_patterns(m);
+  FusedParams fp{};
+  fp.text = r.text;
+  fp.n = r.n;
+  fp.sb = r.sb;
+  fp.se = r.se;
+  fp.span_chunks = r.geo.span_chunks;
+  fp.n_patterns = static_cast<uint32_t>((P + kFuseGroup - 1) / kFuseGroup * kFuseGroup);
+  for (int p = 0; p < static_cast<int>(fp.n_patterns); p++) {
+    rj_scan* s = m->scans[static_cast<size_t>(p < P ? p : 0)];  // padding repeats pattern 0 with no room for hits
+    const DevProgram& D = s->prog->dev;
+    nibble_window(D, 0, &fp.value[p][0], &fp.mask[p][0]);
+    nibble_window(D, D.n_windows > 1 ? 1 : 0, &fp.value[p][1], &fp.mask[p][1]);
+    fp.offset[p] = D.win_offset;
+    fp.len[p] = D.win_len;
+    fp.hits[p] = s->hits.as<uint64_t>();
+    fp.region_cap[p] = p < P ? static_cast<uint32_t>(r.caps[static_cast<size_t>(p)]) : 0;
+    fp.hit_counts[p] = p < P ? s->hit_counts.as<uint32_t>() : m->dummy_counts.as<uint32_t>();
+    fp.zero_counters[p] = p < P ? s->counters.as<unsigned long long>() : nullptr;
+  }
+  static const bool no_prefilter = getenv("RJ_NO_FUSED_PREFILTER") != nullptr;  // measurement override
+  uint32_t bases[2] = {0, 0};
+  const int nb = m->mode == 0 && !no_prefilter ? fused_prefilter_bases(fp, P, bases) : 0;
+  fp.n_bases = static_cast<uint32_t>(nb);
+  if (nb > 0) {
+    fp.base[0] = bases[0];
+    fp.base[1] = bases[nb > 1 ? 1 : 0];
+    for (int p = 0; p < static_cast<int>(fp.n_patterns); p++)
+      for (int w = 0; w < 2; w++) {
+        fp.value[p][w] &= 0x77777777u;
+        fp.mask[p][w] &= 0x77777777u;
+      }
+  }
+  return fp;
+}
+
+// scan_windows_train: the patterns' own scans as one launch; *masked: some window has a wildcard nibble
+TrainParams train_params(rj_multi* m, const MultiRun& r, bool* masked) {
+  const int P = n_patterns(m);
+  TrainParams tp{};
+  tp.text = r.text;
+  tp.n = r.n;
+  tp.sb = r.sb;
+  tp.se = r.se;
+  tp.span_chunks = r.geo.span_chunks;
+  tp.n_patterns = static_cast<uint32_t>(P);
+  *masked = false;
+  for (int p = 0; p < P; p++) {
+    rj_scan* s = m->scans[static_cast<size_t>(p)];
+    const DevProgram& D = s->prog->dev;
+    nibble_window(D, 0, &tp.value[p][0], &tp.mask[p][0]);
+    nibble_window(D, D.n_windows > 1 ? 1 : 0, &tp.value[p][1], &tp.mask[p][1]);
+    *masked = *masked || tp.mask[p][0] != 0xFFFFFFFFu || tp.mask[p][1] != 0xFFFFFFFFu;
+    tp.offset[p] = D.win_offset;
+    tp.len[p] = D.win_len;
+    window_range(r.n, r.sb, r.se, D.win_offset, D.win_len, &tp.wlo[p], &tp.whi[p]);
+    tp.hits[p] = s->hits.as<uint64_t>();
+    tp.region_cap[p] = static_cast<uint32_t>(r.caps[static_cast<size_t>(p)]);
+    tp.hit_counts[p] = s->hit_counts.as<uint32_t>();
+    tp.zero_counters[p] = s->counters.as<unsigned long long>();
+  }
+  return tp;
+}
+
+ScanParams scan_params(rj_multi* m, const MultiRun& r, int p) {
+  rj_scan* s = m->scans[static_cast<size_t>(p)];
+  const DevProgram& D = s->prog->dev;
+  ScanParams sp{};
+  sp.text = r.text;
+  sp.n = r.n;
+  sp.sb = r.sb;
+  sp.se = r.se;
+  window_range(r.n, r.sb, r.se, D.win_offset, D.win_len, &sp.wlo, &sp.whi);
+  sp.span_chunks = r.geo.span_chunks;
+  sp.hits = s->hits.as<uint64_t>();
+  sp.region_cap = static_cast<uint32_t>(r.caps[static_cast<size_t>(p)]);
+  sp.hit_counts = s->hit_counts.as<uint32_t>();
+  sp.zero_counters = s->counters.as<unsigned long long>();
+  return sp;
+}
+
+// the single-pattern tail (verify inside the regions, offsets + gather + check) of pattern p
+MultiTail multi_tail(rj_multi* m, const MultiRun& r, int p) {
+  rj_scan* s = m->scans[static_cast<size_t>(p)];
+  MultiTail t{};
+  t.verify.text = r.text;
+  t.verify.n = r.n;
+  t.verify.hits = s->hits.as<uint64_t>();
+  t.verify.n_regions = r.geo.n_regions;
+  t.verify.region_cap = static_cast<uint32_t>(r.caps[static_cast<size_t>(p)]);
+  t.verify.counters = s->counters.as<unsigned long long>();
+  t.verify.sb = r.sb;
+  t.verify.se = r.se;
+  t.verify.expand = 1;
+  t.verify.float_max = s->prog->dev.float_max;
+  t.program = s->prog->dev;
+  t.hit_counts = s->hit_counts.as<uint32_t>();
+  t.valid_counts = s->valid_counts.as<uint32_t>();
+  t.region_ends = s->cand_end.as<uint64_t>();
+  t.out = s->out.as<uint64_t>();
+  t.out_cap = s->out_cap;
+  t.host_counters = s->host_counters;
+  return t;
+}
+
+// what the classifying kernels read of the shared regions, with the blob of classify_blob
+SharedHits shared_hits_of(rj_multi* m, const MultiRun& r, uint32_t shared_cap) {
   SharedHits sh{};
   sh.hits = m->shared_hits.as<uint64_t>();
   sh.counts = m->shared_counts.as<uint32_t>();
   sh.cap = shared_cap;
-  sh.n_regions = n_regions;
-  sh.n_patterns = static_cast<uint32_t>(P);
+  sh.n_regions = r.geo.n_regions;
+  sh.n_patterns = static_cast<uint32_t>(n_patterns(m));
   sh.win_offset = m->plane.offset;
-  sh.text = d_text;
-  sh.n = n;
-  sh.sb = sb;
-  sh.se = se;
+  sh.text = r.text;
+  sh.n = r.n;
+  sh.sb = r.sb;
+  sh.se = r.se;
   static const bool forward = getenv("RJ_CLASSIFY_FORWARD") != nullptr;  // measurement override
   sh.reverse = forward ? 0u : 1u;
+  sh.blob = m->classify_blob.as<uint32_t>();
+  sh.desc_words = m->desc_words;
+  sh.blob_words = m->blob_words;
   return sh;
+}
+
+// a pattern's window constants and automaton shape, its tables at word `tab` behind the descriptors; no output pointers
+ClassifyDesc classify_desc(const rj_program* prog, uint32_t tab) {
+  const DevProgram& D = prog->dev;
+  const Program& H = *prog->host;
+  ClassifyDesc d{};
+  d.n_windows = static_cast<uint32_t>(std::min(D.n_windows, kClassifyMaxWindows));
+  for (int q = 0; q < kClassifyMaxWindows; q++) {
+    d.v0[q] = D.win_value0[q];
+    d.m0[q] = D.win_mask0[q];
+    d.v1[q] = D.win_value1[q];
+    d.m1[q] = D.win_mask1[q];
+  }
+  d.win_offset = D.win_offset;
+  d.win_len = D.win_len;
+  d.tab = tab;
+  d.n_words = static_cast<uint32_t>(D.n_words);
+  d.n_pos = static_cast<uint32_t>(D.n_pos);
+  d.n_rows = static_cast<uint32_t>(D.n_rows);
+  d.short_max = D.short_max;
+  d.nullable = D.nullable;
+  for (int pos = 0; pos < H.n_pos && pos < 64; pos++) {
+    const int row = H.row_of[static_cast<size_t>(pos)];
+    if (row < 0) continue;
+    bool any = false;
+    for (int k = 0; k < H.n_words; k++) any = any || H.rows[0][static_cast<size_t>(row) * H.n_words + k] != 0;
+    if (any) d.rowbits[pos >> 5] |= 1u << (pos & 31);
+  }
+  return d;
+}
+
+uint32_t padded_table_words(const DevProgram& D) { return (D.table_words + 3u) & ~3u; }
+
+// every pattern's tables into a blob behind `desc_words` words of descriptors, device to device, at the words desc[p].tab
+int copy_tables(rj_multi* m, DeviceBuffer& blob, uint32_t blob_words, uint32_t desc_words, const ClassifyDesc* desc, hipStream_t st) {
+  RJ_HIP(blob.reserve(static_cast<size_t>(blob_words) * sizeof(uint32_t)));
+  RJ_HIP(hipMemsetAsync(blob.p, 0, static_cast<size_t>(blob_words) * sizeof(uint32_t), st));
+  for (int p = 0; p < n_patterns(m); p++) {
+    const DevProgram& D = m->scans[static_cast<size_t>(p)]->prog->dev;
+    RJ_HIP(hipMemcpyAsync(blob.as<uint32_t>() + desc_words + desc[p].tab, D.first, static_cast<size_t>(D.table_words) * sizeof(uint32_t),
+                          hipMemcpyDeviceToDevice, st));
+  }
+  return RJ_OK;
 }
 
 // The blob classify_shared_multi stages in LDS (kernels.h): the tables are copied once, device to device; the
 // descriptors hold this run's output pointers and are uploaded when they changed (host_tails is filled already).
 int classify_blob(rj_multi* m, hipStream_t st) {
-  const int P = static_cast<int>(m->scans.size());
+  const int P = n_patterns(m);
   if (!m->host_desc) RJ_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->host_desc), sizeof(ClassifyDesc) * kMaxFused));
   m->desc_words = static_cast<uint32_t>((sizeof(ClassifyDesc) * static_cast<size_t>(P) + 15) / 16 * 4);
   uint32_t off = 0;
   for (int p = 0; p < P; p++) {
     const MultiTail& t = m->host_tails[p];
-    const DevProgram& D = t.program;
     ClassifyDesc& d = m->host_desc[p];
-    d = ClassifyDesc{};
-    d.n_windows = static_cast<uint32_t>(std::min(D.n_windows, kClassifyMaxWindows));
-    for (int q = 0; q < kClassifyMaxWindows; q++) {
-      d.v0[q] = D.win_value0[q];
-      d.m0[q] = D.win_mask0[q];
-      d.v1[q] = D.win_value1[q];
-      d.m1[q] = D.win_mask1[q];
-    }
-    d.win_offset = D.win_offset;
-    d.win_len = D.win_len;
-    d.tab = off;
-    d.n_words = static_cast<uint32_t>(D.n_words);
-    d.n_pos = static_cast<uint32_t>(D.n_pos);
-    d.n_rows = static_cast<uint32_t>(D.n_rows);
-    d.short_max = D.short_max;
-    d.nullable = D.nullable;
-    {
-      const Program& H = *m->scans[static_cast<size_t>(p)]->prog->host;
-      for (int pos = 0; pos < H.n_pos && pos < 64; pos++) {
-        const int row = H.row_of[static_cast<size_t>(pos)];
-        if (row < 0) continue;
-        bool any = false;
-        for (int k = 0; k < H.n_words; k++) any = any || H.rows[0][static_cast<size_t>(row) * H.n_words + k] != 0;
-        if (any) d.rowbits[pos >> 5] |= 1u << (pos & 31);
-      }
-    }
+    d = classify_desc(m->scans[static_cast<size_t>(p)]->prog, off);
     d.region_cap = t.verify.region_cap;
     d.begins = t.verify.hits;
     d.ends = t.region_ends;
     d.valid_counts = t.valid_counts;
     d.counters = t.verify.counters;
-    off += (D.table_words + 3u) & ~3u;
+    off += padded_table_words(t.program);
   }
   m->blob_words = m->desc_words + off;
   if (!m->classify_tables_ready) {
-    RJ_HIP(m->classify_blob.reserve(static_cast<size_t>(m->blob_words) * sizeof(uint32_t)));
-    RJ_HIP(hipMemsetAsync(m->classify_blob.p, 0, static_cast<size_t>(m->blob_words) * sizeof(uint32_t), st));
-    for (int p = 0; p < P; p++) {
-      const DevProgram& D = m->host_tails[p].program;
-      RJ_HIP(hipMemcpyAsync(m->classify_blob.as<uint32_t>() + m->desc_words + m->host_desc[p].tab, D.first,
-                            static_cast<size_t>(D.table_words) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    }
+    int rc = copy_tables(m, m->classify_blob, m->blob_words, m->desc_words, m->host_desc, st);
+    if (rc != RJ_OK) return rc;
     m->classify_tables_ready = true;
     m->desc_uploaded.clear();
   }
@@ -437,508 +693,347 @@ int classify_blob(rj_multi* m, hipStream_t st) {
   return RJ_OK;
 }
 
-// The scans of all patterns (ONE fused kernel, or one kernel per pattern back to back) + the tails of
-// all patterns in two launches + one synchronise.  Whole text, starts [0, n].
-// phase 0: the whole run (enqueue, synchronise, collect; repeated with larger regions when one overflowed).
-// phase 1 (rj_multi_start): enqueue the first attempt and return.  phase 2 (rj_multi_finish): synchronise and collect
-// what phase 1 enqueued -- same arguments --, and carry on like phase 0 when a region overflowed.
+// the blob the general count kernel stages in LDS: ClassifyDesc per pattern (window constants, table offsets; no output
+// pointers: nothing is written) + the automaton tables, copied device to device from the programs' own
+int count_blob(rj_multi* m, hipStream_t st) {
+  if (m->count_blob_ready) return RJ_OK;
+  const int P = n_patterns(m);
+  std::vector<ClassifyDesc> desc(static_cast<size_t>(P));
+  uint32_t off = 0;
+  for (int p = 0; p < P; p++) {
+    desc[static_cast<size_t>(p)] = classify_desc(m->scans[static_cast<size_t>(p)]->prog, off);
+    off += padded_table_words(m->scans[static_cast<size_t>(p)]->prog->dev);
+  }
+  int rc = copy_tables(m, m->count_blob, m->count_blob_words, m->count_desc_words, desc.data(), st);
+  if (rc != RJ_OK) return rc;
+  // (a pageable source: the runtime stages it before the call returns)
+  RJ_HIP(hipMemcpyAsync(m->count_blob.p, desc.data(), sizeof(ClassifyDesc) * static_cast<size_t>(P), hipMemcpyHostToDevice, st));
+  RJ_HIP(hipStreamSynchronize(st));
+  m->count_blob_ready = true;
+  return RJ_OK;
+}
+
+// ----------------------------------------------------------------------------- small pieces of the run protocol
+// two objects on two streams (rj_multi_order_after): the scan kernels -- both HBM-bound -- stay one behind the
+// other, only the other run's latency-bound tails overlap this scan
+int wait_scan_after(const rj_multi* m, hipStream_t st) {
+  if (m->scan_after != nullptr && m->scan_after != m && m->scan_after->scans[0]->ev[2] != nullptr)
+    RJ_HIP(hipStreamWaitEvent(st, m->scan_after->scans[0]->ev[2], 0));
+  return RJ_OK;
+}
+
+// pending.done behind the run's last kernel, on the stream that holds it
+int record_done(rj_multi* m, hipStream_t st) {
+  if (!m->pending.done) RJ_HIP(hipEventCreateWithFlags(&m->pending.done, hipEventDisableTiming));
+  RJ_HIP(hipEventRecord(m->pending.done, st));
+  return RJ_OK;
+}
+
+// what the span pipeline answers a text of n bytes with: 1 one pass, 2 separate scans + batched tails, 0 one pipeline after the other
+int spans_kind(const rj_multi* m, uint64_t n) { return n < 16 ? 0 : (m->fused && m->mode == 0) ? 1 : m->batchable ? 2 : 0; }
+
+int run_pipelines(rj_multi* m, const MultiRun& r) {
+  for (rj_scan* s : m->scans) {
+    int rc = run_pipeline(s, r.text, r.n, r.sb, r.se, 0, 0, 0, r.st);
+    if (rc != RJ_OK) return rc;
+  }
+  return RJ_OK;
+}
+
+void read_scan_ms(rj_multi* m) {
+  m->scan_ms = 0.f;
+  rj_scan* const s0 = m->scans[0];
+  if (s0->timing) (void)hipEventElapsedTime(&m->scan_ms, s0->ev[1], s0->ev[2]);  // (separate scans: first start to last end, gaps included)
+}
+
+bool plane_scan_v1() {
+  static const bool v1 = getenv("RJ_PLANE_SCAN_V1") != nullptr;   // measurement override
+  return v1;
+}
+
+// ----------------------------------------------------------------------------- the batched pipeline
+// The scans of all patterns (ONE fused kernel, or one kernel per pattern back to back) + the tails of all patterns in two
+// launches + one wait.  enqueue_batched launches one attempt, collect_batched reads its counters once they are in: done
+// (RJ_OK), kAgain (a region overflowed: the hints have grown, enqueue again), or kRegionsFull.
 // (internal) the batched pipeline's regions cannot hold this text's hits -- a text with a hit at (almost) every position:
 // the caller runs every pattern's own pipeline, which has the dense and the large paths for that
-constexpr int kRegionsFull = -100;
-int run_batched(rj_multi* m, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, hipStream_t st, bool fuse, int phase = 0) {
-  const int P = static_cast<int>(m->scans.size());
+constexpr int kRegionsFull = -100, kAgain = -101;
+constexpr int kBatchedAttempts = 6;
+
+// (in place: pending.run keeps the storage of `caps` from one rj_multi_start to the next)
+void set_run(MultiRun& r, const void* d_text, uint64_t n, uint64_t sb, uint64_t se, void* hip_stream) {
+  r.text = static_cast<const uint8_t*>(d_text);
+  r.n = n;
+  r.sb = sb;
+  r.se = se;
+  r.st = static_cast<hipStream_t>(hip_stream);
+}
+
+// the geometry of a batched run; fuse: one scan kernel for all patterns (kind 1)
+void plan_batched(const rj_multi* m, MultiRun& r, bool fuse) {
   // chunks that can hold a window of a start in [sb, se): a window begins at most 7 bytes after its start
-  const uint64_t end_byte = std::min<uint64_t>(n, se + 8);
-  uint64_t chunks = std::max<uint64_t>((end_byte + 1023) / 1024 - sb / 1024, 1);
+  const uint64_t end_byte = std::min<uint64_t>(r.n, r.se + 8);
+  uint64_t chunks = std::max<uint64_t>((end_byte + 1023) / 1024 - r.sb / 1024, 1);
   // mode 0, every window within one byte of <= 2 bases: the bit-plane scan (plane_scan.hip), which walks the
   // window positions [wlo, whi) in pairs of chunks
   static const bool no_plane = getenv("RJ_NO_PLANE") != nullptr;  // measurement override
-  const bool plane = fuse && m->mode == 0 && m->plane.ok && !no_plane;
-  if (fuse && m->plane.general && !plane) fuse = false;  // (a general set has no other one-pass kernel: separate scans, batched tails)
-  uint64_t plane_pairs = 0, plane_wlo = 0, plane_whi = 0;
-  if (plane) {
-    // window positions that can belong to a start in [sb, se): the general plan's patterns have their own offsets
-    const uint32_t cmp = m->plane.general ? m->plane.n_cmp : 8u;
-    plane_wlo = sb + (m->plane.general ? m->plane.min_offset : m->plane.offset);
-    const uint64_t last_w = n >= cmp ? n - cmp + 1 : 0;
-    plane_whi = std::min<uint64_t>(se + (m->plane.general ? m->plane.max_offset : m->plane.offset), last_w);
-    plane_pairs = plane_whi > plane_wlo ? (plane_whi + 2047) / 2048 - plane_wlo / 2048 : 0;
-    chunks = std::max<uint64_t>(plane_pairs * 2, 1);
+  r.plane = fuse && m->mode == 0 && m->plane.ok && !no_plane;
+  r.fuse = fuse && (r.plane || !m->plane.general);  // (a general set has no other one-pass kernel: separate scans, batched tails)
+  if (r.plane) {
+    r.blocks = blocks_of(m->plane, r.n, r.sb, r.se);
+    chunks = std::max<uint64_t>(r.blocks.blocks() * 2, 1);
   }
   // (plane scan, 500 MB: 96 chunks per workgroup measured best -- 92 us against 98 at 128, 96 at 64)
   static const int plane_chunks = getenv("RJ_PLANE_CHUNKS") ? atoi(getenv("RJ_PLANE_CHUNKS")) : 96;  // measurement override
-  const ScanGeometry geo = scan_geometry(chunks, plane ? static_cast<uint64_t>(plane_chunks > 0 ? plane_chunks : 96) : 128);
+  r.geo = scan_geometry(chunks, r.plane ? static_cast<uint64_t>(plane_chunks > 0 ? plane_chunks : 96) : 128);
+  r.caps.assign(m->scans.size(), 0);
+}
+
+// this attempt's regions of every pattern (from its hint) and of the shared candidates; the scans' results are reset
+int regions_for_attempt(rj_multi* m, MultiRun& r) {
+  const ScanGeometry& geo = r.geo;
+  RJ_HIP(m->dummy_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
+  for (size_t p = 0; p < m->scans.size(); p++) {
+    rj_scan* s = m->scans[p];
+    const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(s->region_cap_hint, 64), geo.span_chunks * 1024);
+    r.caps[p] = cap;
+    int rc = ensure_lists(s, geo.n_regions, static_cast<uint32_t>(cap), static_cast<uint64_t>(geo.n_regions) * cap);
+    if (rc != RJ_OK) return rc;
+    RJ_HIP(s->valid_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
+    s->stats = rj_stats{};
+    s->result = nullptr;
+    s->result_count = 0;
+  }
+  r.shared_cap = 0;
+  if (r.plane) {
+    r.shared_cap = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint32_t>(m->shared_cap_hint, 64), r.blocks.span_pairs(geo.n_regions) * 2048));
+    RJ_HIP(m->shared_hits.reserve(static_cast<size_t>(geo.n_regions) * r.shared_cap * sizeof(uint64_t)));
+    RJ_HIP(m->shared_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
+  }
+  return RJ_OK;
+}
+
+// the tails' parameters travel as one small array, uploaded when it changed
+int upload_tails(rj_multi* m, const MultiRun& r) {
+  const int P = n_patterns(m);
+  for (int p = 0; p < P; p++) {
+    m->host_tails[p] = multi_tail(m, r, p);
+    m->scans[static_cast<size_t>(p)]->host_counters[kCntUnordered] = 0;
+    m->scans[static_cast<size_t>(p)]->host_counters[kCntAdjacent] = 0;
+  }
+  if (m->uploaded.size() != static_cast<size_t>(P) || memcmp(m->uploaded.data(), m->host_tails, sizeof(MultiTail) * static_cast<size_t>(P)) != 0) {
+    RJ_HIP(hipMemcpyAsync(m->tails.p, m->host_tails, sizeof(MultiTail) * P, hipMemcpyHostToDevice, r.st));
+    m->uploaded.assign(m->host_tails, m->host_tails + P);
+  }
+  return RJ_OK;
+}
+
+// the bit-plane scan of the regexdna shape: candidates to the shared regions, or classified in the kernel (sets r.fused_launched)
+int enqueue_plane_scan(rj_multi* m, MultiRun& r) {
   rj_scan* const s0 = m->scans[0];
-  std::vector<uint64_t> caps(static_cast<size_t>(P));
-  uint32_t shared_cap = 0;
-  bool fused_launched = false;  // this attempt's scan kernel classified its own candidates (plane_scan_classify)
-  for (int attempt = 0; attempt < 6; attempt++) {
-   if (phase == 2 && attempt == 0) {
-    caps = m->pending.caps;
-    shared_cap = m->pending.shared_cap;
-    fused_launched = m->last_was_fused_classify;
-   } else {
-    FusedParams fp{};
-    fp.text = d_text;
-    fp.n = n;
-    fp.sb = sb;
-    fp.se = se;
-    fp.span_chunks = geo.span_chunks;
-    fp.n_patterns = static_cast<uint32_t>((P + kFuseGroup - 1) / kFuseGroup * kFuseGroup);
-    RJ_HIP(m->dummy_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
-    for (int p = 0; p < static_cast<int>(fp.n_patterns); p++) {
-      const int q = p < P ? p : 0;  // padding repeats pattern 0 with no room for hits
-      rj_scan* s = m->scans[static_cast<size_t>(q)];
-      const DevProgram& D = s->prog->dev;
-      nibble_window(D, 0, &fp.value[p][0], &fp.mask[p][0]);
-      nibble_window(D, D.n_windows > 1 ? 1 : 0, &fp.value[p][1], &fp.mask[p][1]);
-      fp.offset[p] = D.win_offset;
-      fp.len[p] = D.win_len;
-      if (p < P) {
-        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(s->region_cap_hint, 64), geo.span_chunks * 1024);
-        caps[static_cast<size_t>(p)] = cap;
-        int rc = ensure_lists(s, geo.n_regions, static_cast<uint32_t>(cap), static_cast<uint64_t>(geo.n_regions) * cap);
-        if (rc != RJ_OK) return rc;
-        RJ_HIP(s->valid_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
-        fp.hits[p] = s->hits.as<uint64_t>();
-        fp.region_cap[p] = static_cast<uint32_t>(cap);
-        fp.hit_counts[p] = s->hit_counts.as<uint32_t>();
-        fp.zero_counters[p] = s->counters.as<unsigned long long>();
-        s->stats = rj_stats{};
-        s->result = nullptr;
-        s->result_count = 0;
-      } else {
-        fp.hits[p] = m->scans[0]->hits.as<uint64_t>();
-        fp.region_cap[p] = 0;
-        fp.hit_counts[p] = m->dummy_counts.as<uint32_t>();
-        fp.zero_counters[p] = nullptr;
+  const PlaneParams pp = plane_params(m, r);
+  // plane_scan_classify (scan + classification in one kernel): correct, but measured no faster than the two kernels
+  // -- its classification is VALU work inside a kernel that is VALU co-limited (scan 99 -> 119 us per 500 MB, step
+  // 0.152 ms either way) -- so it is opt-in (tests run both)
+  static const bool want_fused_classify = getenv("RJ_FUSED_CLASSIFY") != nullptr;
+  if (m->fused_classify && (want_fused_classify || m->want_fused_classify)) {
+    int rc = classify_blob(m, r.st);
+    if (rc != RJ_OK) return rc;
+    const SharedHits sh = shared_hits_of(m, r, 0);
+    if (sh.blob_words <= kFusedMaxBlobWords) {
+      if (!m->flags_clean) {
+        for (rj_scan* s : m->scans) RJ_HIP(hipMemsetAsync(s->counters.p, 0, kCntSize * sizeof(unsigned long long), r.st));
+        m->flags_clean = true;
       }
+      r.fused_launched = launch_plane_scan_classify(pp, sh, m->max_words, m->max_short, s0->counters.as<unsigned long long>(), r.geo.grid,
+                                                    s0->t0(), s0->ev[2], r.st);
     }
-    fp.n_bases = 0;
-    static const bool no_prefilter = getenv("RJ_NO_FUSED_PREFILTER") != nullptr;  // measurement override
-    if (fuse && m->mode == 0 && !no_prefilter) {
-      // Shared prefilter (kernels.hip: fused_chunk_d1): are all windows within one nibble of <= 2 base
-      // windows?  Nibbles are compared on their low 3 bits there.  A base is a window without
-      // wildcards; greedy: the first uncovered exact window becomes the next base.
-      auto nibbles_off = [](uint32_t v, uint32_t k, uint32_t base) {  // nibbles in which (v, k) leaves `base` free or differs
-        int d = 0;
-        for (int i = 0; i < 8; i++) {
-          const uint32_t kk = (k >> (4 * i)) & 7u, vv = (v >> (4 * i)) & 7u, bb = (base >> (4 * i)) & 7u;
-          d += (kk == 0 || vv != bb) ? 1 : 0;
-        }
-        return d;
-      };
-      uint32_t bases[2] = {0, 0};
-      int nb = 0;
-      bool ok = true;
-      for (int pass = 0; pass < 2 && ok; pass++)
-        for (int p = 0; p < P && ok; p++)
-          for (int w = 0; w < 2 && ok; w++) {
-            const uint32_t v = fp.value[p][w] & 0x77777777u, k = fp.mask[p][w] & 0x77777777u;
-            bool covered = false;
-            for (int b = 0; b < nb; b++) covered = covered || nibbles_off(v, k, bases[b]) <= 1;
-            if (covered) continue;
-            if (pass == 0) {
-              if (k == 0x77777777u && nb < 2) bases[nb++] = v;  // an exact window: a new base
-            } else {
-              ok = false;  // second pass: still not within one nibble of a base
-            }
-          }
-      if (ok && nb > 0) {
-        fp.n_bases = static_cast<uint32_t>(nb);
-        fp.base[0] = bases[0];
-        fp.base[1] = bases[nb > 1 ? 1 : 0];
-        for (int p = 0; p < static_cast<int>(fp.n_patterns); p++)
-          for (int w = 0; w < 2; w++) {
-            fp.value[p][w] &= 0x77777777u;
-            fp.mask[p][w] &= 0x77777777u;
-          }
-      }
-    }
-    // the single-pattern tails (verify inside the regions, offsets + gather + check) of all patterns
-    // in two launches; their parameters travel as one small array
-    for (int p = 0; p < P; p++) {
-      rj_scan* s = m->scans[static_cast<size_t>(p)];
-      MultiTail& t = m->host_tails[p];
-      t = MultiTail{};
-      t.verify.text = d_text;
-      t.verify.n = n;
-      t.verify.hits = s->hits.as<uint64_t>();
-      t.verify.n_regions = geo.n_regions;
-      t.verify.region_cap = static_cast<uint32_t>(caps[static_cast<size_t>(p)]);
-      t.verify.counters = s->counters.as<unsigned long long>();
-      t.verify.sb = sb;
-      t.verify.se = se;
-      t.verify.expand = 1;
-      t.verify.float_max = s->prog->dev.float_max;
-      t.program = s->prog->dev;
-      t.hit_counts = s->hit_counts.as<uint32_t>();
-      t.valid_counts = s->valid_counts.as<uint32_t>();
-      t.region_ends = s->cand_end.as<uint64_t>();
-      t.out = s->out.as<uint64_t>();
-      t.out_cap = s->out_cap;
-      t.host_counters = s->host_counters;
-      s->host_counters[kCntUnordered] = 0;
-      s->host_counters[kCntAdjacent] = 0;
-    }
-    if (m->uploaded.size() != static_cast<size_t>(P) ||
-        memcmp(m->uploaded.data(), m->host_tails, sizeof(MultiTail) * static_cast<size_t>(P)) != 0) {
-      RJ_HIP(hipMemcpyAsync(m->tails.p, m->host_tails, sizeof(MultiTail) * P, hipMemcpyHostToDevice, st));
-      m->uploaded.assign(m->host_tails, m->host_tails + P);
-    }
-    shared_cap = 0;
-    if (m->scan_after != nullptr && m->scan_after != m && m->scan_after->scans[0]->ev[2] != nullptr) {
-      // two objects on two streams (rj_multi_order_after): the scan kernels -- both HBM-bound -- stay one behind the
-      // other, only the other run's latency-bound tails overlap this scan
-      RJ_HIP(hipStreamWaitEvent(st, m->scan_after->scans[0]->ev[2], 0));
-    }
-    if (plane && m->plane.general) {
-      PlaneGParams pg{};
-      pg.text = d_text;
-      pg.n = n;
-      pg.wlo = plane_wlo;
-      pg.whi = plane_whi;
-      pg.span_pairs = std::max<uint64_t>((plane_pairs + geo.n_regions - 1) / geo.n_regions, 1);
-      pg.code_shift = m->plane.code_shift;
-      pg.n_bases = m->plane.n_bases;
-      pg.n_cmp = m->plane.n_cmp;
-      pg.tolerance = m->plane.tolerance;
-      for (uint32_t b = 0; b < kPlaneMaxBases; b++)
-        for (int i = 0; i < 8; i++) {
-          const uint32_t code = (static_cast<uint32_t>(m->plane.base[b < m->plane.n_bases ? b : 0][i]) >> m->plane.code_shift) & 3u;
-          pg.lo[b][i] = (code & 1u) ? 0u : ~0u;
-          pg.hi[b][i] = (code & 2u) ? 0u : ~0u;
-        }
-      shared_cap = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint32_t>(m->shared_cap_hint, 64), pg.span_pairs * 2048));
-      RJ_HIP(m->shared_hits.reserve(static_cast<size_t>(geo.n_regions) * shared_cap * sizeof(uint64_t)));
-      RJ_HIP(m->shared_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
-      pg.hits = m->shared_hits.as<uint64_t>();
-      pg.region_cap = shared_cap;
-      pg.hit_counts = m->shared_counts.as<uint32_t>();
-      pg.n_zero = static_cast<uint32_t>(P);
-      for (int p = 0; p < P; p++) pg.zero_counters[p] = m->scans[static_cast<size_t>(p)]->counters.as<unsigned long long>();
-      fused_launched = false;
+  }
+  if (r.fused_launched) return RJ_OK;
+  m->flags_clean = false;
+  // round 6: plane_count's streaming loop (32 contiguous bytes per lane, code planes through the VGPR index mode, the
+  // blocks dealt out evenly) with the candidates written to the shared regions: plane_scan<NB> is kept behind RJ_PLANE_SCAN_V1
+  if (plane_scan_v1()) launch_plane_scan(pp, r.geo.grid, s0->t0(), s0->ev[2], r.st);
+  else launch_plane_list(plane_list_params(m, r), r.geo.grid, s0->t0(), s0->ev[2], r.st);
+  return RJ_OK;
+}
+
+// every pattern's own scan kernel (each at its full streaming rate), queued back to back on
+// the caller's stream -- or, mode 2, alternating between it and a second stream: kernels of ONE
+// stream run strictly one after the other, so every kernel boundary costs the drain of the
+// last workgroups plus the ramp-up of the next grid; with two streams the next kernel's
+// workgroups fill the slots as they become free (regexdna step 0.95 -> 0.89 ms)
+// (mode 2 only: the kernels of the two streams overlap in time, so a per-kernel duration no
+// longer means what a roofline needs; the default keeps them on the caller's stream)
+int enqueue_separate_scans(rj_multi* m, const MultiRun& r) {
+  const int P = n_patterns(m);
+  rj_scan* const s0 = m->scans[0];
+  hipStream_t st = r.st;
+  const bool two_streams = m->mode == 2;
+  // mode 1, every pattern with the regexdna shape (two nibble-form windows): the scans as one launch
+  static const bool no_train = getenv("RJ_NO_TRAIN") != nullptr;  // measurement override
+  bool train = m->mode == 1 && !no_train;  // (mode 3: one launch per pattern, as round 1 did)
+  for (int p = 0; p < P && train; p++) train = fusable(m->scans[static_cast<size_t>(p)]->prog);
+  if (train) {
+    bool masked = false;
+    const TrainParams tp = train_params(m, r, &masked);
+    launch_scan_windows_train(tp, masked, r.geo.grid, s0->t0(), s0->ev[2], st);
+  }
+  if (two_streams) {
+    RJ_HIP(hipEventRecord(m->fork, st));
+    RJ_HIP(hipStreamWaitEvent(m->second, m->fork, 0));
+  }
+  for (int p = 0; p < P && !train; p++) {
+    rj_scan* s = m->scans[static_cast<size_t>(p)];
+    // one pair of timestamps around the whole train of scan kernels (first kernel's start, last
+    // kernel's end): a pair per kernel puts a completion signal between consecutive kernels
+    launch_scan_windows(scan_params(m, r, p), make_window_set(s->prog), s->prog->dev.n_windows, r.geo.grid, p == 0 ? s0->t0() : nullptr,
+                        (!two_streams && p == P - 1) ? s0->ev[2] : nullptr, (two_streams && (p & 1)) ? m->second : st);
+  }
+  if (two_streams) {
+    RJ_HIP(hipEventRecord(m->join, m->second));
+    RJ_HIP(hipStreamWaitEvent(st, m->join, 0));
+    RJ_HIP(hipEventRecord(s0->ev[2], st));  // end of the train: both streams have drained
+  }
+  return RJ_OK;
+}
+
+// ts: the stream of what follows the scan kernel -- r.st, or the object's own stream (rj_multi_start)
+int enqueue_batched(rj_multi* m, MultiRun& r, hipStream_t ts) {
+  const int P = n_patterns(m);
+  rj_scan* const s0 = m->scans[0];
+  int rc = regions_for_attempt(m, r);
+  if (rc == RJ_OK) rc = upload_tails(m, r);
+  if (rc == RJ_OK) rc = wait_scan_after(m, r.st);
+  if (rc != RJ_OK) return rc;
+  r.fused_launched = false;
+  if (r.plane && m->plane.general) {
+    m->flags_clean = false;
+    // round 6: plane_count's streaming loop with the general test (code planes through the VGPR index mode), the candidates
+    // written to the shared regions; plane_scan_general is kept behind RJ_PLANE_SCAN_V1
+    if (plane_scan_v1()) launch_plane_scan_general(plane_g_params(m, r), r.geo.grid, s0->t0(), s0->ev[2], r.st);
+    else launch_plane_list_general(plane_list_g_params(m, r), r.geo.grid, s0->t0(), s0->ev[2], r.st);
+  } else if (r.plane) {
+    rc = enqueue_plane_scan(m, r);
+  } else if (r.fuse) {
+    launch_scan_windows_fused(fused_params(m, r), r.geo.grid, s0->t0(), s0->ev[2], r.st);
+  } else {
+    rc = enqueue_separate_scans(m, r);
+  }
+  if (rc != RJ_OK) return rc;
+  // rj_multi_set_tail_stream: everything behind the scan goes to the object's own stream, ordered by the scan's end
+  // event -- the caller's stream is free for the next scan kernel (of another rj_multi) at once
+  if (ts != r.st) RJ_HIP(hipStreamWaitEvent(ts, s0->ev[2], 0));
+  if (r.plane && r.fused_launched) {
+    launch_offsets_gather_check_multi(m->tails.as<MultiTail>(), P, r.geo.n_regions, ts);
+  } else if (r.plane) {
+    rc = classify_blob(m, ts);
+    if (rc != RJ_OK) return rc;
+    const SharedHits sh = shared_hits_of(m, r, r.shared_cap);
+    if (m->plane.general) launch_tails_shared_general(m->tails.as<MultiTail>(), sh, m->max_words, m->max_short, s0->counters.as<unsigned long long>(), ts);
+    else launch_tails_shared(m->tails.as<MultiTail>(), sh, m->max_words, m->max_short, s0->counters.as<unsigned long long>(), ts);
+  } else {
+    launch_tails_multi(m->tails.as<MultiTail>(), P, r.geo.n_regions, ts);
+  }
+  return RJ_OK;
+}
+
+// after the wait for enqueue_batched's kernels: attempt 0 is the run's first
+int collect_batched(rj_multi* m, MultiRun& r, int attempt) {
+  const int P = n_patterns(m);
+  rj_scan* const s0 = m->scans[0];
+  const ScanGeometry& geo = r.geo;
+  bool again = false;
+  if (r.plane && r.fused_launched) {
+    // the flags plane_scan_classify sets but does not clear: dirty when any of them is up
+    for (rj_scan* s : m->scans)
+      if (s->host_counters[kCntOverflow] != 0) m->flags_clean = false;
+    if (s0->host_counters[kCntSharedMax] != 0) {
+      // a span with more candidates than the kernel's LDS slots: the two kernels with shared regions in device memory
       m->flags_clean = false;
-      // round 6: plane_count's streaming loop with the general test (code planes through the VGPR index mode), the candidates
-      // written to the shared regions; plane_scan_general is kept behind RJ_PLANE_SCAN_V1
-      static const bool v1g = getenv("RJ_PLANE_SCAN_V1") != nullptr;   // measurement override
-      if (v1g) {
-        launch_plane_scan_general(pg, geo.grid, s0->t0(), s0->ev[2], st);
-      } else {
-        PlaneListGParams pl{};
-        PlaneCountParams& c = pl.g.c;
-        c.text = d_text;
-        c.n = n;
-        c.sb = sb;
-        c.se = se;
-        c.first_block = plane_wlo / 2048;
-        c.end_block = c.first_block + plane_pairs;
-        c.span_blocks = plane_pairs / geo.n_regions;
-        c.span_extra = static_cast<uint32_t>(plane_pairs % geo.n_regions);
-        c.code_shift = m->plane.code_shift;
-        c.n_bases = m->plane.n_bases;
-        c.n_patterns = static_cast<uint32_t>(P);
-        c.batch_at = 64;
-        pl.g.n_cmp = m->plane.n_cmp;
-        pl.g.tolerance = m->plane.tolerance;
-        for (uint32_t b = 0; b < kPlaneMaxBases; b++)
-          for (uint32_t i = 0; i < 8; i++)
-            pl.g.idx[b][i] = i < m->plane.n_cmp ? (static_cast<uint32_t>(m->plane.base[b < m->plane.n_bases ? b : 0][i]) >> m->plane.code_shift) & 3u : 4u;
-        pl.hits = pg.hits;
-        pl.region_cap = pg.region_cap;
-        pl.offset = 0;
-        pl.hit_counts = pg.hit_counts;
-        pl.n_zero = pg.n_zero;
-        for (uint32_t p = 0; p < pg.n_zero; p++) pl.zero_counters[p] = pg.zero_counters[p];
-        launch_plane_list_general(pl, geo.grid, s0->t0(), s0->ev[2], st);
-      }
-    } else if (plane) {
-      PlaneParams pp{};
-      pp.text = d_text;
-      pp.n = n;
-      pp.sb = sb;
-      pp.se = se;
-      pp.span_pairs = std::max<uint64_t>((plane_pairs + geo.n_regions - 1) / geo.n_regions, 1);
-      pp.offset = m->plane.offset;
-      pp.code_shift = m->plane.code_shift;
-      pp.n_bases = m->plane.n_bases;
-      for (uint32_t b = 0; b < 2; b++)
-        for (int i = 0; i < 8; i++) {
-          const uint32_t code = (static_cast<uint32_t>(m->plane.base[b < m->plane.n_bases ? b : 0][i]) >> m->plane.code_shift) & 3u;
-          pp.lo[b][i] = (code & 1u) ? 0u : ~0u;
-          pp.hi[b][i] = (code & 2u) ? 0u : ~0u;
-        }
-      shared_cap = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint32_t>(m->shared_cap_hint, 64), pp.span_pairs * 2048));
-      RJ_HIP(m->shared_hits.reserve(static_cast<size_t>(geo.n_regions) * shared_cap * sizeof(uint64_t)));
-      RJ_HIP(m->shared_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
-      pp.hits = m->shared_hits.as<uint64_t>();
-      pp.region_cap = shared_cap;
-      pp.hit_counts = m->shared_counts.as<uint32_t>();
-      pp.n_zero = static_cast<uint32_t>(P);
-      for (int p = 0; p < P; p++) pp.zero_counters[p] = m->scans[static_cast<size_t>(p)]->counters.as<unsigned long long>();
-      // plane_scan_classify (scan + classification in one kernel): correct, but measured no faster than the two kernels
-      // -- its classification is VALU work inside a kernel that is VALU co-limited (scan 99 -> 119 us per 500 MB, step
-      // 0.152 ms either way) -- so it is opt-in (tests run both)
-      static const bool want_fused_classify = getenv("RJ_FUSED_CLASSIFY") != nullptr;
-      fused_launched = false;
-      if (m->fused_classify && (want_fused_classify || m->want_fused_classify)) {
-        const SharedHits sh = shared_hits_of(m, d_text, n, sb, se, 0, geo.n_regions, P);
-        int rc = classify_blob(m, st);
-        if (rc != RJ_OK) return rc;
-        SharedHits shb = sh;
-        shb.blob = m->classify_blob.as<uint32_t>();
-        shb.desc_words = m->desc_words;
-        shb.blob_words = m->blob_words;
-        if (shb.blob_words <= kFusedMaxBlobWords) {
-          if (!m->flags_clean) {
-            for (int p = 0; p < P; p++)
-              RJ_HIP(hipMemsetAsync(m->scans[static_cast<size_t>(p)]->counters.p, 0, kCntSize * sizeof(unsigned long long), st));
-            m->flags_clean = true;
-          }
-          int max_words = 1;
-          uint32_t max_short = 0;
-          for (int p = 0; p < P; p++) {
-            const DevProgram& D = m->scans[static_cast<size_t>(p)]->prog->dev;
-            max_words = std::max(max_words, static_cast<int>(D.n_words));
-            max_short = std::max(max_short, D.short_max);
-          }
-          fused_launched = launch_plane_scan_classify(pp, shb, max_words, max_short, s0->counters.as<unsigned long long>(), geo.grid,
-                                                      s0->t0(), s0->ev[2], st);
-        }
-      }
-      if (!fused_launched) {
-        m->flags_clean = false;
-        // round 6: plane_count's streaming loop (32 contiguous bytes per lane, code planes through the VGPR index mode, the
-        // blocks dealt out evenly) with the candidates written to the shared regions: plane_scan<NB> is kept behind RJ_PLANE_SCAN_V1
-        static const bool v1 = getenv("RJ_PLANE_SCAN_V1") != nullptr;   // measurement override
-        if (v1) {
-          launch_plane_scan(pp, geo.grid, s0->t0(), s0->ev[2], st);
-        } else {
-          PlaneListParams pl{};
-          pl.c.text = d_text;
-          pl.c.n = n;
-          pl.c.sb = sb;
-          pl.c.se = se;
-          pl.c.first_block = plane_wlo / 2048;
-          pl.c.end_block = pl.c.first_block + plane_pairs;
-          pl.c.span_blocks = plane_pairs / geo.n_regions;
-          pl.c.span_extra = static_cast<uint32_t>(plane_pairs % geo.n_regions);
-          pl.c.code_shift = m->plane.code_shift;
-          pl.c.n_bases = m->plane.n_bases;
-          pl.c.n_patterns = static_cast<uint32_t>(P);
-          pl.c.batch_at = 64;
-          for (uint32_t b = 0; b < 2; b++) {
-            const uint32_t bb = b < m->plane.n_bases ? b : 0;
-            for (int i = 0; i < 8; i++) {
-              const uint32_t code = (static_cast<uint32_t>(m->plane.base[bb][i]) >> m->plane.code_shift) & 3u;
-              if (!(code & 1u)) pl.c.mask_bits |= 1u << (16 * b + 2 * i);
-              if (!(code & 2u)) pl.c.mask_bits |= 1u << (16 * b + 2 * i + 1);
-            }
-          }
-          pl.hits = pp.hits;
-          pl.region_cap = pp.region_cap;
-          pl.offset = pp.offset;
-          pl.hit_counts = pp.hit_counts;
-          pl.n_zero = pp.n_zero;
-          for (uint32_t p = 0; p < pp.n_zero; p++) pl.zero_counters[p] = pp.zero_counters[p];
-          launch_plane_list(pl, geo.grid, s0->t0(), s0->ev[2], st);
-        }
-      }
-    } else if (fuse) {
-      launch_scan_windows_fused(fp, geo.grid, s0->t0(), s0->ev[2], st);
-    } else {
-      // every pattern's own scan kernel (each at its full streaming rate), queued back to back on
-      // the caller's stream -- or, mode 2, alternating between it and a second stream: kernels of ONE
-      // stream run strictly one after the other, so every kernel boundary costs the drain of the
-      // last workgroups plus the ramp-up of the next grid; with two streams the next kernel's
-      // workgroups fill the slots as they become free (regexdna step 0.95 -> 0.89 ms)
-      // (mode 2 only: the kernels of the two streams overlap in time, so a per-kernel duration no
-      // longer means what a roofline needs; the default keeps them on the caller's stream)
-      const bool two_streams = m->mode == 2;
-      // mode 1, every pattern with the regexdna shape (two nibble-form windows): the scans as one launch
-      static const bool no_train = getenv("RJ_NO_TRAIN") != nullptr;  // measurement override
-      bool train = m->mode == 1 && !no_train;  // (mode 3: one launch per pattern, as round 1 did)
-      for (int p = 0; p < P && train; p++) train = fusable(m->scans[static_cast<size_t>(p)]->prog);
-      if (train) {
-        TrainParams tp{};
-        tp.text = d_text;
-        tp.n = n;
-        tp.sb = sb;
-        tp.se = se;
-        tp.span_chunks = geo.span_chunks;
-        tp.n_patterns = static_cast<uint32_t>(P);
-        bool masked = false;
-        for (int p = 0; p < P; p++) {
-          rj_scan* s = m->scans[static_cast<size_t>(p)];
-          const DevProgram& D = s->prog->dev;
-          tp.value[p][0] = fp.value[p][0];
-          tp.mask[p][0] = fp.mask[p][0];
-          tp.value[p][1] = fp.value[p][1];
-          tp.mask[p][1] = fp.mask[p][1];
-          masked = masked || fp.mask[p][0] != 0xFFFFFFFFu || fp.mask[p][1] != 0xFFFFFFFFu;
-          tp.offset[p] = D.win_offset;
-          tp.len[p] = D.win_len;
-          tp.wlo[p] = sb + D.win_offset;
-          const uint64_t last_w = n >= D.win_len ? n - D.win_len + 1 : 0;
-          tp.whi[p] = std::min<uint64_t>(se + D.win_offset, last_w);
-          if (tp.whi[p] < tp.wlo[p]) tp.whi[p] = tp.wlo[p];
-          tp.hits[p] = s->hits.as<uint64_t>();
-          tp.region_cap[p] = static_cast<uint32_t>(caps[static_cast<size_t>(p)]);
-          tp.hit_counts[p] = s->hit_counts.as<uint32_t>();
-          tp.zero_counters[p] = s->counters.as<unsigned long long>();
-        }
-        launch_scan_windows_train(tp, masked, geo.grid, s0->t0(), s0->ev[2], st);
-      }
-      if (two_streams) {
-        RJ_HIP(hipEventRecord(m->fork, st));
-        RJ_HIP(hipStreamWaitEvent(m->second, m->fork, 0));
-      }
-      for (int p = 0; p < P && !train; p++) {
-        rj_scan* s = m->scans[static_cast<size_t>(p)];
-        const DevProgram& D = s->prog->dev;
-        ScanParams sp{};
-        sp.text = d_text;
-        sp.n = n;
-        sp.sb = sb;
-        sp.se = se;
-        sp.wlo = sb + D.win_offset;
-        const uint64_t last_w = n >= D.win_len ? n - D.win_len + 1 : 0;
-        sp.whi = std::min<uint64_t>(se + D.win_offset, last_w);
-        if (sp.whi < sp.wlo) sp.whi = sp.wlo;
-        sp.span_chunks = geo.span_chunks;
-        sp.hits = s->hits.as<uint64_t>();
-        sp.region_cap = static_cast<uint32_t>(caps[static_cast<size_t>(p)]);
-        sp.hit_counts = s->hit_counts.as<uint32_t>();
-        sp.zero_counters = s->counters.as<unsigned long long>();
-        // one pair of timestamps around the whole train of scan kernels (first kernel's start, last
-        // kernel's end): a pair per kernel puts a completion signal between consecutive kernels
-        hipStream_t sp_stream = (two_streams && (p & 1)) ? m->second : st;
-        launch_scan_windows(sp, make_window_set(s->prog), D.n_windows, geo.grid, p == 0 ? s0->t0() : nullptr,
-                            (!two_streams && p == P - 1) ? s0->ev[2] : nullptr, sp_stream);
-      }
-      if (two_streams) {
-        RJ_HIP(hipEventRecord(m->join, m->second));
-        RJ_HIP(hipStreamWaitEvent(st, m->join, 0));
-        RJ_HIP(hipEventRecord(s0->ev[2], st));  // end of the train: both streams have drained
-      }
+      m->fused_classify = false;
+      m->shared_cap_hint = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(s0->host_counters[kCntSharedMax] * 2, m->shared_cap_hint), 1u << 20));
+      return kAgain;
     }
-    // rj_multi_set_tail_stream: everything behind the scan goes to the object's own stream, ordered by the scan's end
-    // event -- the caller's stream is free for the next scan kernel (of another rj_multi) at once
-    hipStream_t ts = st;
-    if (phase == 1 && m->tails_own_stream && m->tail_stream != nullptr && m->mode != 2) {
-      ts = m->tail_stream;
-      RJ_HIP(hipStreamWaitEvent(ts, s0->ev[2], 0));
-    }
-    if (plane && fused_launched) {
-      launch_offsets_gather_check_multi(m->tails.as<MultiTail>(), P, geo.n_regions, ts);
-    } else if (plane) {
-      SharedHits sh = shared_hits_of(m, d_text, n, sb, se, shared_cap, geo.n_regions, P);
-      int rc = classify_blob(m, ts);
-      if (rc != RJ_OK) return rc;
-      sh.blob = m->classify_blob.as<uint32_t>();
-      sh.desc_words = m->desc_words;
-      sh.blob_words = m->blob_words;
-      int max_words = 1;
-      uint32_t max_short = 0;
-      for (int p = 0; p < P; p++) {
-        const DevProgram& D = m->scans[static_cast<size_t>(p)]->prog->dev;
-        max_words = std::max(max_words, static_cast<int>(D.n_words));
-        max_short = std::max(max_short, D.short_max);
-      }
-      if (m->plane.general) launch_tails_shared_general(m->tails.as<MultiTail>(), sh, max_words, max_short, s0->counters.as<unsigned long long>(), ts);
-      else launch_tails_shared(m->tails.as<MultiTail>(), sh, max_words, max_short, s0->counters.as<unsigned long long>(), ts);
-    } else {
-      launch_tails_multi(m->tails.as<MultiTail>(), P, geo.n_regions, ts);
-    }
-    if (phase == 1) {
-      if (!m->pending.done) RJ_HIP(hipEventCreateWithFlags(&m->pending.done, hipEventDisableTiming));
-      RJ_HIP(hipEventRecord(m->pending.done, ts));
-    }
-   }
-    if (phase == 1) {
-      m->pending.caps = caps;
-      m->pending.shared_cap = shared_cap;
-      m->last_was_fused_classify = fused_launched;
-      return RJ_OK;  // (pending.done was recorded behind the tails, on the stream that holds them)
-    }
-    // (phase 2: the stream may already hold the NEXT run of another rj_multi -- wait for this one only)
-    if (phase == 2 && attempt == 0) RJ_HIP(hipEventSynchronize(m->pending.done));
-    else RJ_HIP(hipStreamSynchronize(st));
-    RJ_HIP(hipGetLastError());
-    bool again = false;
-    if (plane && fused_launched) {
-      // the flags plane_scan_classify sets but does not clear: dirty when any of them is up
-      for (int p = 0; p < P; p++)
-        if (m->scans[static_cast<size_t>(p)]->host_counters[kCntOverflow] != 0) m->flags_clean = false;
-      if (s0->host_counters[kCntSharedMax] != 0) {
-        // a span with more candidates than the kernel's LDS slots: the two kernels with shared regions in device memory
-        m->flags_clean = false;
-        m->fused_classify = false;
-        m->shared_cap_hint = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(s0->host_counters[kCntSharedMax] * 2, m->shared_cap_hint), 1u << 20));
-        s0->stats.retries++;
-        continue;
-      }
-    } else if (plane && s0->host_counters[kCntSharedMax] != 0) {
-      // a shared candidate region overflowed: size them all for the fullest one seen (x2) and run again
-      const uint64_t want = std::max<uint64_t>(s0->host_counters[kCntSharedMax] * 2, static_cast<uint64_t>(shared_cap) * 2);
-      if (shared_cap >= 2048 * std::max<uint64_t>((plane_pairs + geo.n_regions - 1) / geo.n_regions, 1))
-        return kRegionsFull;   // (run_spans: one pipeline after the other)
-      m->shared_cap_hint = static_cast<uint32_t>(std::min<uint64_t>(want, 1u << 20));
+  } else if (r.plane && s0->host_counters[kCntSharedMax] != 0) {
+    // a shared candidate region overflowed: size them all for the fullest one seen (x2) and run again
+    const uint64_t want = std::max<uint64_t>(s0->host_counters[kCntSharedMax] * 2, static_cast<uint64_t>(r.shared_cap) * 2);
+    if (r.shared_cap >= 2048 * r.blocks.span_pairs(geo.n_regions)) return kRegionsFull;   // (run_spans: one pipeline after the other)
+    m->shared_cap_hint = static_cast<uint32_t>(std::min<uint64_t>(want, 1u << 20));
+    again = true;
+  }
+  for (int p = 0; p < P; p++) {
+    rj_scan* s = m->scans[static_cast<size_t>(p)];
+    if (s->host_counters[kCntOverflow] != 0) {
+      const uint64_t cap = r.caps[static_cast<size_t>(p)];
+      const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(s->host_counters[kCntMaxRegion] * 2, cap * 4), geo.span_chunks * 1024);
+      if (want <= cap) return kRegionsFull;
+      s->region_cap_hint = static_cast<uint32_t>(std::min<uint64_t>(want, 1u << 20));
       again = true;
     }
-    for (int p = 0; p < P; p++) {
-      rj_scan* s = m->scans[static_cast<size_t>(p)];
-      if (s->host_counters[kCntOverflow] != 0) {
-        const uint64_t cap = caps[static_cast<size_t>(p)];
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(s->host_counters[kCntMaxRegion] * 2, cap * 4), geo.span_chunks * 1024);
-        if (want <= cap) return kRegionsFull;
-        s->region_cap_hint = static_cast<uint32_t>(std::min<uint64_t>(want, 1u << 20));
-        again = true;
-      }
-    }
-    if (!s0->timing) {
-      m->scan_ms = 0.f;
-    } else if (fuse) {
-      if (s0->timing) (void)hipEventElapsedTime(&m->scan_ms, s0->ev[1], s0->ev[2]);
-    } else {
-      if (s0->timing) (void)hipEventElapsedTime(&m->scan_ms, s0->ev[1], s0->ev[2]);  // first start to last end, gaps included
-    }
-    if (again) continue;
-    for (int p = 0; p < P; p++) {
-      rj_scan* s = m->scans[static_cast<size_t>(p)];
-      hipStream_t sp = st;  // (rare) selection kernels of one pattern after the other
-      if (s->host_counters[kCntOverrun] != 0) {
-        // a long-lived candidate: this pattern's run is void; its own pipeline takes the carry scan
-        s->linear_hint = true;
-        int rc = run_pipeline(s, d_text, n, sb, se, 0, 0, 0, st);
-        if (rc != RJ_OK) return rc;
-        continue;
-      }
-      s->hits_hint = s->host_counters[kCntHits];
-      s->stats.n_hits = s->host_counters[kCntHits];
-      FinalizeParams sel{};
-      sel.carry_cur = 0;
-      sel.carry_prev_end = 0;
-      sel.have_prev = 0;
-      if (s->host_counters[kCntUnordered] != 0) {
-        const uint64_t nc = s->host_counters[kCntCands];
-        RJ_HIP(s->keys_out.reserve(nc * sizeof(uint64_t)));
-        RJ_HIP(s->vals_out.reserve(nc * sizeof(uint64_t)));
-        launch_split_pairs(s->out.as<uint64_t>(), s->counters.as<unsigned long long>() + kCntCands, nc,
-                           s->keys_out.as<uint64_t>(), s->vals_out.as<uint64_t>(), sp);
-      }
-      int rc = resolve_selection(s, sel, sp);
+  }
+  read_scan_ms(m);
+  if (again) return kAgain;
+  for (int p = 0; p < P; p++) {
+    rj_scan* s = m->scans[static_cast<size_t>(p)];
+    hipStream_t sp = r.st;  // (rare) selection kernels of one pattern after the other
+    if (s->host_counters[kCntOverrun] != 0) {
+      // a long-lived candidate: this pattern's run is void; its own pipeline takes the carry scan
+      s->linear_hint = true;
+      int rc = run_pipeline(s, r.text, r.n, r.sb, r.se, 0, 0, 0, r.st);
       if (rc != RJ_OK) return rc;
-      s->result = s->out.as<uint64_t>();
-      s->stats.n_matches = s->result_count;
-      s->stats.scan_ms = fuse ? m->scan_ms : m->scan_ms / static_cast<float>(P);
+      continue;
     }
-    return RJ_OK;
+    s->hits_hint = s->host_counters[kCntHits];
+    s->stats.n_hits = s->host_counters[kCntHits];
+    s->stats.retries = attempt;   // (the attempts before this one: every enqueue resets the scans' stats)
+    FinalizeParams sel{};
+    sel.carry_cur = 0;
+    sel.carry_prev_end = 0;
+    sel.have_prev = 0;
+    if (s->host_counters[kCntUnordered] != 0) {
+      const uint64_t nc = s->host_counters[kCntCands];
+      RJ_HIP(s->keys_out.reserve(nc * sizeof(uint64_t)));
+      RJ_HIP(s->vals_out.reserve(nc * sizeof(uint64_t)));
+      launch_split_pairs(s->out.as<uint64_t>(), s->counters.as<unsigned long long>() + kCntCands, nc,
+                         s->keys_out.as<uint64_t>(), s->vals_out.as<uint64_t>(), sp);
+    }
+    int rc = resolve_selection(s, sel, sp);
+    if (rc != RJ_OK) return rc;
+    s->result = s->out.as<uint64_t>();
+    s->stats.n_matches = s->result_count;
+    s->stats.scan_ms = r.fuse ? m->scan_ms : m->scan_ms / static_cast<float>(P);
+  }
+  return RJ_OK;
+}
+
+// enqueue, wait for the caller's stream, collect -- from attempt `first` on, with larger regions while one overflows
+int run_batched(rj_multi* m, MultiRun& r, int first = 0) {
+  for (int attempt = first; attempt < kBatchedAttempts; attempt++) {
+    int rc = enqueue_batched(m, r, r.st);
+    if (rc != RJ_OK) return rc;
+    RJ_HIP(hipStreamSynchronize(r.st));
+    RJ_HIP(hipGetLastError());
+    rc = collect_batched(m, r, attempt);
+    if (rc != kAgain) return rc;
   }
   return kRegionsFull;
 }
 
+// the span lists of every pattern over the run's starts, synchronously: what rj_multi_run does without the counts switch
+// (1 one pass, 2 separate scans + batched tails, 0 one pipeline after the other; < 0 rj_status)
+int run_spans(rj_multi* m, MultiRun& r) {
+  const int kind = spans_kind(m, r.n);
+  if (kind != 0) {
+    plan_batched(m, r, kind == 1);
+    int rc = run_batched(m, r);
+    if (rc != kRegionsFull) return rc != RJ_OK ? rc : kind;
+  }
+  int rc = run_pipelines(m, r);
+  return rc != RJ_OK ? rc : 0;
+}
 
+// ----------------------------------------------------------------------------- the count kernel
 bool counts_shape(const rj_multi* m) {
   return (m->exact.ok && m->plane.ok && !m->plane.general && m->plane.offset == 0) || m->general_counts;
 }
@@ -948,185 +1043,82 @@ bool counts_path(const rj_multi* m) {
   return m->counts_only && counts_shape(m) && m->mode == 0 && !off;
 }
 
-// the blob the general count kernel stages in LDS: ClassifyDesc per pattern (window constants, table offsets; no output
-// pointers: nothing is written) + the automaton tables, copied device to device from the programs' own
-int count_blob(rj_multi* m, hipStream_t st) {
-  if (m->count_blob_ready) return RJ_OK;
-  const int P = static_cast<int>(m->scans.size());
-  std::vector<ClassifyDesc> desc(static_cast<size_t>(P));
-  RJ_HIP(m->count_blob.reserve(static_cast<size_t>(m->count_blob_words) * sizeof(uint32_t)));
-  RJ_HIP(hipMemsetAsync(m->count_blob.p, 0, static_cast<size_t>(m->count_blob_words) * sizeof(uint32_t), st));
-  uint32_t off = 0;
-  for (int p = 0; p < P; p++) {
-    const DevProgram& D = m->scans[static_cast<size_t>(p)]->prog->dev;
-    const Program& H = *m->scans[static_cast<size_t>(p)]->prog->host;
-    ClassifyDesc& d = desc[static_cast<size_t>(p)];
-    d = ClassifyDesc{};
-    d.n_windows = static_cast<uint32_t>(std::min(D.n_windows, kClassifyMaxWindows));
-    for (int q = 0; q < kClassifyMaxWindows; q++) {
-      d.v0[q] = D.win_value0[q];
-      d.m0[q] = D.win_mask0[q];
-      d.v1[q] = D.win_value1[q];
-      d.m1[q] = D.win_mask1[q];
+// MatchAllCount of every pattern over the starts [sb, se) in one kernel: enqueue_counts launches it and the sum of its
+// rows (on ts, as enqueue_batched), collect_counts reads the result once it is in.  A void run (flags) is repeated by the span pipeline,
+// synchronously -- THAT run: the next one tries the kernel again (round 5 left the object on the span pipeline for good
+// after one tandem repeat).
+int enqueue_counts(rj_multi* m, MultiRun& r, hipStream_t ts) {
+  rj_scan* const s0 = m->scans[0];
+  hipStream_t st = r.st;
+  const bool general = !(m->exact.ok && m->plane.ok && !m->plane.general && m->plane.offset == 0);
+  const PlanePlan& plan = general ? m->gplane : m->plane;
+  r.blocks = blocks_of(plan, r.n, r.sb, r.se);
+  // (500 MB, rounds 5-6 before the stash: 2048 .. 3584 workgroups measured equal, 0.094 ms; 5086 0.0985, 8192 0.101: a wave's
+  // fixed costs want long spans.  With the stash four workgroups of ExactShape are resident per CU (35 KB of LDS each) and the
+  // grid matters: KiB per workgroup 64 / 96 / 112 / 120 / 128 / 136 / 144 / 160 / 240 / 320 / 440 / 480 / 520 -> the kernel inside
+  // the two-in-flight loop 0.0915 / 0.0869 / 0.0879 / 0.0895 / 0.0851 / 0.0860 / 0.0867 / 0.0870 / 0.0875 / 0.0906 / 0.1064 / 0.0860 /
+  // 0.0915 ms -- 440 is 1109 workgroups, a second round of 85 behind the 1024 resident ones; 128 is the generic scans' share too)
+  static const int count_chunks = getenv("RJ_COUNT_CHUNKS") ? atoi(getenv("RJ_COUNT_CHUNKS")) : 128;  // measurement override
+  r.geo = scan_geometry(std::max<uint64_t>(r.blocks.blocks() * 2, 1), static_cast<uint64_t>(count_chunks > 0 ? count_chunks : 128));
+  const ScanGeometry& geo = r.geo;
+  if (!m->counts_ready) {
+    if (!m->count_out) RJ_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->count_out), sizeof(unsigned long long) * kPcHostWords));
+    if (m->exact.ok) {
+      RJ_HIP(m->exact_table.reserve(sizeof(uint32_t) * kExactTabWords));
+      RJ_HIP(hipMemcpyAsync(m->exact_table.p, m->exact.table, sizeof(uint32_t) * kExactTabWords, hipMemcpyHostToDevice, st));
     }
-    d.win_offset = D.win_offset;
-    d.win_len = D.win_len;
-    d.tab = off;
-    d.n_words = static_cast<uint32_t>(D.n_words);
-    d.n_pos = static_cast<uint32_t>(D.n_pos);
-    d.n_rows = static_cast<uint32_t>(D.n_rows);
-    d.short_max = D.short_max;
-    d.nullable = D.nullable;
-    for (int pos = 0; pos < H.n_pos && pos < 64; pos++) {
-      const int row = H.row_of[static_cast<size_t>(pos)];
-      if (row < 0) continue;
-      bool any = false;
-      for (int k = 0; k < H.n_words; k++) any = any || H.rows[0][static_cast<size_t>(row) * H.n_words + k] != 0;
-      if (any) d.rowbits[pos >> 5] |= 1u << (pos & 31);
-    }
-    RJ_HIP(hipMemcpyAsync(m->count_blob.as<uint32_t>() + m->count_desc_words + off, D.first, static_cast<size_t>(D.table_words) * sizeof(uint32_t),
-                          hipMemcpyDeviceToDevice, st));
-    off += (D.table_words + 3u) & ~3u;
+    RJ_HIP(m->count_acc.reserve(sizeof(unsigned long long) * kPcAccWords));
+    RJ_HIP(hipMemsetAsync(m->count_acc.p, 0, sizeof(unsigned long long) * kPcAccWords, st));
+    m->counts_ready = true;   // (only now: a failure above leaves the next call to start over)
   }
-  // (a pageable source: the runtime stages it before the call returns)
-  RJ_HIP(hipMemcpyAsync(m->count_blob.p, desc.data(), sizeof(ClassifyDesc) * static_cast<size_t>(P), hipMemcpyHostToDevice, st));
-  RJ_HIP(hipStreamSynchronize(st));
-  m->count_blob_ready = true;
+  static const int batch_env = getenv("RJ_COUNT_BATCH") ? atoi(getenv("RJ_COUNT_BATCH")) : 64;  // measurement override
+  const uint32_t batch_at = static_cast<uint32_t>(std::min(std::max(batch_env, 1), 64));
+  PlaneCountGParams pg{};
+  if (general) {
+    int rc = count_blob(m, st);
+    if (rc != RJ_OK) return rc;
+    pg = plane_count_g_params(m, plan, r, batch_at);
+    pg.lmax = m->max_short;
+    pg.desc_words = m->count_desc_words;
+    pg.c.table = m->count_blob.as<uint32_t>();
+    pg.c.table_words = m->count_blob_words;
+  } else {
+    pg.c = plane_count_params(m, plan, r, batch_at);
+    pg.c.mask_bits = plane_mask_bits(plan.base, plan.n_bases, plan.code_shift);
+    for (uint32_t b = 0; b < 2; b++) {
+      pg.c.base_lo[b] = m->exact.base_lo[b < plan.n_bases ? b : 0];
+      pg.c.base_hi[b] = m->exact.base_hi[b < plan.n_bases ? b : 0];
+    }
+    pg.c.table = m->exact_table.as<uint32_t>();
+  }
+  PlaneCountParams& pc = pg.c;
+  pc.acc = m->count_acc.as<unsigned long long>();
+  pc.host_out = m->count_out;
+  RJ_HIP(m->wg_rows.reserve(sizeof(uint32_t) * kExactMaxPatterns * static_cast<size_t>(geo.grid)));
+  RJ_HIP(m->wg_bounds.reserve(sizeof(unsigned long long) * 2 * kExactMaxPatterns * static_cast<size_t>(geo.grid)));
+  pc.wg_rows = m->wg_rows.as<uint32_t>();
+  pc.wg_bounds = m->wg_bounds.as<unsigned long long>();
+  int rc = wait_scan_after(m, st);
+  if (rc != RJ_OK) return rc;
+  if (general) launch_plane_count_general(pg, m->max_words, m->max_short, geo.grid, s0->t0(), s0->ev[2], st);
+  else launch_plane_count(pc, geo.grid, s0->t0(), s0->ev[2], st);
+  // the rows added up: behind the scan, on the object's own stream when the caller keeps runs in flight (rj_multi_start):
+  // the caller's stream is free for the next scan kernel at once
+  if (ts != st) RJ_HIP(hipStreamWaitEvent(ts, s0->ev[2], 0));
+  launch_plane_count_finish(pc, geo.grid, ts);
   return RJ_OK;
 }
 
-// the span lists of every pattern over the starts [sb, se), synchronously: what rj_multi_run does without the counts switch
-// (1 one pass, 2 separate scans + batched tails, 0 one pipeline after the other; < 0 rj_status)
-int run_spans(rj_multi* m, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, hipStream_t st) {
-  if (m->fused && m->mode == 0 && n >= 16) {
-    int rc = run_batched(m, d_text, n, sb, se, st, true);
-    if (rc != kRegionsFull) return rc != RJ_OK ? rc : 1;
-  } else if (m->batchable && n >= 16) {
-    int rc = run_batched(m, d_text, n, sb, se, st, false);
-    if (rc != kRegionsFull) return rc != RJ_OK ? rc : 2;
-  }
-  for (rj_scan* s : m->scans) {
-    int rc = run_pipeline(s, d_text, n, sb, se, 0, 0, 0, st);
-    if (rc != RJ_OK) return rc;
-  }
-  return 0;
-}
-
-// MatchAllCount of every pattern over the starts [sb, se) in one kernel.  phase as run_batched.  A void run (flags) is
-// repeated by the span pipeline, synchronously -- THAT run: the next one tries the kernel again (round 5 left the object
-// on the span pipeline for good after one tandem repeat).
-int run_counts(rj_multi* m, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, hipStream_t st, int phase) {
-  const int P = static_cast<int>(m->scans.size());
-  rj_scan* const s0 = m->scans[0];
-  if (phase != 2) {
-    // window positions that can belong to a start in [sb, se): the general plan's patterns have their own offsets
-    const bool general = !(m->exact.ok && m->plane.ok && !m->plane.general && m->plane.offset == 0);
-    const PlanePlan& plan = general ? m->gplane : m->plane;
-    const uint32_t cmp = general ? plan.n_cmp : 8u;
-    const uint64_t last_w = n >= cmp ? n - cmp + 1 : 0;
-    const uint64_t wlo = sb + (general ? plan.min_offset : 0u), whi = std::min<uint64_t>(se + (general ? plan.max_offset : 0u), last_w);
-    const uint64_t first_block = wlo / 2048;
-    const uint64_t end_block = whi > wlo ? (whi + 2047) / 2048 : first_block;
-    const uint64_t blocks = end_block - first_block;
-    // (500 MB, rounds 5-6 before the stash: 2048 .. 3584 workgroups measured equal, 0.094 ms; 5086 0.0985, 8192 0.101: a wave's
-    // fixed costs want long spans.  With the stash four workgroups of ExactShape are resident per CU (35 KB of LDS each) and the
-    // grid matters: KiB per workgroup 64 / 96 / 112 / 120 / 128 / 136 / 144 / 160 / 240 / 320 / 440 / 480 / 520 -> the kernel inside
-    // the two-in-flight loop 0.0915 / 0.0869 / 0.0879 / 0.0895 / 0.0851 / 0.0860 / 0.0867 / 0.0870 / 0.0875 / 0.0906 / 0.1064 / 0.0860 /
-    // 0.0915 ms -- 440 is 1109 workgroups, a second round of 85 behind the 1024 resident ones; 128 is the generic scans' share too)
-    static const int count_chunks = getenv("RJ_COUNT_CHUNKS") ? atoi(getenv("RJ_COUNT_CHUNKS")) : 128;  // measurement override
-    const ScanGeometry geo = scan_geometry(std::max<uint64_t>(blocks * 2, 1), static_cast<uint64_t>(count_chunks > 0 ? count_chunks : 128));
-    if (!m->counts_ready) {
-      if (!m->count_out) RJ_HIP(hipHostMalloc(reinterpret_cast<void**>(&m->count_out), sizeof(unsigned long long) * kPcHostWords));
-      if (m->exact.ok) {
-        RJ_HIP(m->exact_table.reserve(sizeof(uint32_t) * kExactTabWords));
-        RJ_HIP(hipMemcpyAsync(m->exact_table.p, m->exact.table, sizeof(uint32_t) * kExactTabWords, hipMemcpyHostToDevice, st));
-      }
-      RJ_HIP(m->count_acc.reserve(sizeof(unsigned long long) * kPcAccWords));
-      RJ_HIP(hipMemsetAsync(m->count_acc.p, 0, sizeof(unsigned long long) * kPcAccWords, st));
-      m->counts_ready = true;   // (only now: a failure above leaves the next call to start over)
-    }
-    PlaneCountParams pc{};
-    pc.text = d_text;
-    pc.n = n;
-    pc.sb = sb;
-    pc.se = se;
-    pc.first_block = first_block;
-    pc.end_block = end_block;
-    pc.span_blocks = blocks / geo.n_regions;
-    pc.span_extra = static_cast<uint32_t>(blocks % geo.n_regions);
-    pc.code_shift = plan.code_shift;
-    pc.n_bases = plan.n_bases;
-    pc.n_patterns = static_cast<uint32_t>(P);
-    static const int batch_at = getenv("RJ_COUNT_BATCH") ? atoi(getenv("RJ_COUNT_BATCH")) : 64;  // measurement override
-    pc.batch_at = static_cast<uint32_t>(std::min(std::max(batch_at, 1), 64));
-    PlaneCountGParams pg{};
-    if (general) {
-      int rc = count_blob(m, st);
-      if (rc != RJ_OK) return rc;
-      pc.table = m->count_blob.as<uint32_t>();
-      pc.table_words = m->count_blob_words;
-      pg.n_cmp = plan.n_cmp;
-      pg.tolerance = plan.tolerance;
-      pg.lmax = m->count_lmax;
-      pg.desc_words = m->count_desc_words;
-      for (uint32_t b = 0; b < kPlaneMaxBases; b++)
-        for (uint32_t i = 0; i < 8; i++)
-          pg.idx[b][i] = i < plan.n_cmp ? (static_cast<uint32_t>(plan.base[b < plan.n_bases ? b : 0][i]) >> plan.code_shift) & 3u : 4u;
-    } else {
-      for (uint32_t b = 0; b < 2; b++) {
-        const uint32_t bb = b < plan.n_bases ? b : 0;
-        for (int i = 0; i < 8; i++) {
-          const uint32_t code = (static_cast<uint32_t>(plan.base[bb][i]) >> plan.code_shift) & 3u;
-          if (!(code & 1u)) pc.mask_bits |= 1u << (16 * b + 2 * i);
-          if (!(code & 2u)) pc.mask_bits |= 1u << (16 * b + 2 * i + 1);
-        }
-        pc.base_lo[b] = m->exact.base_lo[bb];
-        pc.base_hi[b] = m->exact.base_hi[bb];
-      }
-      pc.table = m->exact_table.as<uint32_t>();
-    }
-    pc.acc = m->count_acc.as<unsigned long long>();
-    pc.host_out = m->count_out;
-    RJ_HIP(m->wg_rows.reserve(sizeof(uint32_t) * kExactMaxPatterns * static_cast<size_t>(geo.grid)));
-    RJ_HIP(m->wg_bounds.reserve(sizeof(unsigned long long) * 2 * kExactMaxPatterns * static_cast<size_t>(geo.grid)));
-    pc.wg_rows = m->wg_rows.as<uint32_t>();
-    pc.wg_bounds = m->wg_bounds.as<unsigned long long>();
-    if (m->scan_after != nullptr && m->scan_after != m && m->scan_after->scans[0]->ev[2] != nullptr)
-      RJ_HIP(hipStreamWaitEvent(st, m->scan_after->scans[0]->ev[2], 0));
-    if (general) {
-      pg.c = pc;
-      launch_plane_count_general(pg, m->count_max_words, m->count_max_short, geo.grid, s0->t0(), s0->ev[2], st);
-    } else {
-      launch_plane_count(pc, geo.grid, s0->t0(), s0->ev[2], st);
-    }
-    // the rows added up: behind the scan, on the object's own stream when the caller keeps runs in flight (rj_multi_start):
-    // the caller's stream is free for the next scan kernel at once
-    hipStream_t fs = st;
-    if (phase == 1) {
-      if (!m->tail_stream) RJ_HIP(hipStreamCreateWithFlags(&m->tail_stream, hipStreamNonBlocking));
-      fs = m->tail_stream;
-      RJ_HIP(hipStreamWaitEvent(fs, s0->ev[2], 0));
-    }
-    launch_plane_count_finish(pc, geo.grid, fs);
-    if (phase == 1) {
-      if (!m->pending.done) RJ_HIP(hipEventCreateWithFlags(&m->pending.done, hipEventDisableTiming));
-      RJ_HIP(hipEventRecord(m->pending.done, fs));
-      return RJ_OK;
-    }
-  }
-  if (phase == 2) RJ_HIP(hipEventSynchronize(m->pending.done));
-  else RJ_HIP(hipStreamSynchronize(st));
-  RJ_HIP(hipGetLastError());
+int collect_counts(rj_multi* m, MultiRun& r) {
   if (m->count_out[kPcHostFlags] != 0) {
     m->counts_fallbacks++;
     m->last_counts = false;
-    int kind = run_spans(m, d_text, n, sb, se, st);
+    int kind = run_spans(m, r);
     return kind < 0 ? kind : RJ_OK;
   }
-  m->scan_ms = 0.f;
-  if (s0->timing) (void)hipEventElapsedTime(&m->scan_ms, s0->ev[1], s0->ev[2]);
-  for (int p = 0; p < P; p++) {
-    rj_scan* s = m->scans[static_cast<size_t>(p)];
+  read_scan_ms(m);
+  for (size_t p = 0; p < m->scans.size(); p++) {
+    rj_scan* s = m->scans[p];
     s->stats = rj_stats{};
     s->result = nullptr;   // (no span list: rj_scan_device_spans reads NULL, the readers of the list refuse)
     s->result_count = m->count_out[kPcHostCount + p];
@@ -1170,6 +1162,8 @@ int rj_multi_create(const rj_program* const* progs, int n_progs, rj_multi** out)
     }
     m->scans.push_back(s);
     all = all && fusable(progs[i]);
+    m->max_words = std::max(m->max_words, static_cast<int>(progs[i]->dev.n_words));
+    m->max_short = std::max(m->max_short, progs[i]->dev.short_max);
     all_batchable = all_batchable && batchable(progs[i]);
   }
   if (m->tails.reserve(sizeof(MultiTail) * static_cast<size_t>(n_progs)) != hipSuccess ||
@@ -1216,13 +1210,10 @@ int rj_multi_create(const rj_program* const* progs, int n_progs, rj_multi** out)
       const Program& H = *s->prog->host;
       ok = ok && !H.has_assertions && !H.q8_risk && !H.any_nullable && H.min_len >= 1 && D.short_max >= 1 && D.short_max <= 16 && D.n_words <= 2;
       words += (D.table_words + 3u) & ~3u;
-      m->count_lmax = std::max(m->count_lmax, D.short_max);
-      m->count_max_short = std::max(m->count_max_short, D.short_max);
-      m->count_max_words = std::max(m->count_max_words, static_cast<int>(D.n_words));
     }
     m->count_desc_words = static_cast<uint32_t>((sizeof(ClassifyDesc) * static_cast<size_t>(n_progs) + 15) / 16 * 4);
     m->count_blob_words = m->count_desc_words + words;
-    m->general_counts = ok && m->count_blob_words <= kCountMaxBlobWords && n_progs < kExactMaxPatterns && m->count_lmax >= 2;
+    m->general_counts = ok && m->count_blob_words <= kCountMaxBlobWords && n_progs < kExactMaxPatterns && m->max_short >= 2;
   }
   {
     std::lock_guard<std::mutex> lock(live_multi_mutex());
@@ -1273,15 +1264,21 @@ int rj_multi_run_range(rj_multi* m, const void* d_text, uint64_t n, uint64_t own
   }
   if ((reinterpret_cast<uintptr_t>(d_text) & 15u) != 0) return fail(RJ_BAD_ARGUMENT, "device text must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  MultiRun r;
+  set_run(r, d_text, n, own_begin, own_end, hip_stream);
   m->scan_ms = 0.f;
   int fused = 0;
   m->last_counts = false;
   if (n >= 16 && counts_path(m)) {
-    int rc = run_counts(m, static_cast<const uint8_t*>(d_text), n, own_begin, own_end, st, 0);
+    int rc = enqueue_counts(m, r, st);
     if (rc != RJ_OK) return rc;
-    fused = m->last_counts ? 3 : (m->fused && m->mode == 0) ? 1 : m->batchable ? 2 : 0;
+    RJ_HIP(hipStreamSynchronize(st));
+    RJ_HIP(hipGetLastError());
+    rc = collect_counts(m, r);
+    if (rc != RJ_OK) return rc;
+    fused = m->last_counts ? 3 : spans_kind(m, n);   // (a void run: the span pipeline answered)
   } else {
-    fused = run_spans(m, static_cast<const uint8_t*>(d_text), n, own_begin, own_end, st);
+    fused = run_spans(m, r);
     if (fused < 0) return fused;
   }
   for (size_t i = 0; i < m->scans.size(); i++) counts[i] = m->scans[i]->result_count;
@@ -1295,22 +1292,25 @@ int rj_multi_start(rj_multi* m, const void* d_text, uint64_t n, uint64_t own_beg
   if ((reinterpret_cast<uintptr_t>(d_text) & 15u) != 0) return fail(RJ_BAD_ARGUMENT, "device text must be 16-byte aligned");
   if (own_end > n + 1) own_end = n + 1;
   rj_multi::Pending& q = m->pending;
-  q.text = static_cast<const uint8_t*>(d_text);
-  q.n = n;
-  q.sb = own_begin;
-  q.se = own_end;
-  q.st = static_cast<hipStream_t>(hip_stream);
+  MultiRun& r = q.run;
+  set_run(r, d_text, n, own_begin, own_end, hip_stream);
   m->scan_ms = 0.f;
-  q.kind = own_begin >= own_end ? -1 : (n >= 16 && counts_path(m)) ? 3 : (m->fused && m->mode == 0 && n >= 16) ? 1 : (m->batchable && n >= 16) ? 2 : 0;
-  q.fuse = q.kind == 1;
+  q.kind = own_begin >= own_end ? -1 : (n >= 16 && counts_path(m)) ? 3 : spans_kind(m, n);
   m->last_counts = false;
+  int rc = RJ_OK;
+  hipStream_t ts = r.st;   // (whatever rj_multi_finish has to run again stays on the caller's stream)
   if (q.kind == 3) {
-    int rc = run_counts(m, q.text, n, q.sb, q.se, q.st, 1);
-    if (rc != RJ_OK) return rc;
+    // (the sum of the rows always goes to the object's own stream, made at the first such run)
+    if (!m->tail_stream) RJ_HIP(hipStreamCreateWithFlags(&m->tail_stream, hipStreamNonBlocking));
+    ts = m->tail_stream;
+    rc = enqueue_counts(m, r, ts);
   } else if (q.kind > 0) {
-    int rc = run_batched(m, q.text, n, q.sb, q.se, q.st, q.fuse, 1);
-    if (rc != RJ_OK) return rc;
+    plan_batched(m, r, q.kind == 1);
+    if (m->tails_own_stream && m->tail_stream != nullptr && m->mode != 2) ts = m->tail_stream;
+    rc = enqueue_batched(m, r, ts);
   }  // (kind 0: pattern sets that take one pipeline after the other run in rj_multi_finish)
+  if (rc == RJ_OK && q.kind > 0) rc = record_done(m, ts);
+  if (rc != RJ_OK) return rc;
   q.active = true;
   return RJ_OK;
 }
@@ -1325,26 +1325,27 @@ int rj_multi_finish(rj_multi* m, uint64_t* counts) {
     for (size_t i = 0; i < m->scans.size(); i++) counts[i] = 0;
     return 0;
   }
+  MultiRun& r = q.run;
+  if (q.kind > 0) {
+    // (the stream may already hold the NEXT run of another rj_multi -- wait for this one only)
+    RJ_HIP(hipEventSynchronize(q.done));
+    RJ_HIP(hipGetLastError());
+  }
+  int rc = RJ_OK;
   if (q.kind == 3) {
-    int rc = run_counts(m, q.text, q.n, q.sb, q.se, q.st, 2);
-    if (rc != RJ_OK) return rc;
-    if (!m->last_counts) q.kind = (m->fused && m->mode == 0) ? 1 : m->batchable ? 2 : 0;   // (a void run: the span pipeline answered)
+    rc = collect_counts(m, r);
+    if (rc == RJ_OK && !m->last_counts) q.kind = spans_kind(m, r.n);   // (a void run: the span pipeline answered)
   } else if (q.kind != 0) {
-    int rc = run_batched(m, q.text, q.n, q.sb, q.se, q.st, q.fuse, 2);
+    rc = collect_batched(m, r, 0);
+    if (rc == kAgain) rc = run_batched(m, r, 1);
     if (rc == kRegionsFull) {   // (a hit at almost every position: every pattern's own pipeline)
       q.kind = 0;
-      for (rj_scan* s : m->scans) {
-        rc = run_pipeline(s, q.text, q.n, q.sb, q.se, 0, 0, 0, q.st);
-        if (rc != RJ_OK) return rc;
-      }
+      rc = run_pipelines(m, r);
     }
-    if (rc != RJ_OK) return rc;
   } else {
-    for (rj_scan* s : m->scans) {
-      int rc = run_pipeline(s, q.text, q.n, q.sb, q.se, 0, 0, 0, q.st);
-      if (rc != RJ_OK) return rc;
-    }
+    rc = run_pipelines(m, r);
   }
+  if (rc != RJ_OK) return rc;
   for (size_t i = 0; i < m->scans.size(); i++) counts[i] = m->scans[i]->result_count;
   return q.kind;
 }

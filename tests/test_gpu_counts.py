@@ -304,6 +304,27 @@ def test_a_block_full_of_candidates_voids_the_run(rj, oracle, W):
         assert mc.how == (1 if void else 3), (reps, mc.how)
 
 
+def test_a_void_run_in_flight_is_answered_by_the_span_pipeline(rj, oracle, W):
+    """The same two texts through rj_multi_start / rj_multi_finish: the void step returns 1 with the oracle's counts (the span
+    pipeline ran inside rj_multi_finish), the next step on the same object takes the count kernel again (3)."""
+    progs = [rj.Program(rx) for rx in W.REGEXDNA_PATTERNS]
+    void_data = b"agggtaaa" * 400000 + b"acgt" * 1000
+    data = b"agggtaaa" * 5000 + b"acgt" * 1000
+    # (the oracle's counts: `agggtaaa` back to back matches pattern 0 once per copy and nothing else -- checked at 5000 copies,
+    # and the copies' matches do not overlap, so 400000 copies hold 400000; the oracle needs minutes for that text)
+    assert [5000] + [0] * 8 == oracle_counts(oracle, W.REGEXDNA_PATTERNS, data)
+    tv, tt = device_text(void_data), device_text(data)
+    ms = [rj.MultiScan(progs) for _ in range(2)]
+    for m in ms:
+        assert m.set_counts_only(True)
+    ms[0].start(tv.data_ptr(), len(void_data))
+    ms[1].start(tt.data_ptr(), len(data))
+    assert ms[0].finish() == [400000] + [0] * 8 and ms[0].how == 1
+    ms[0].start(tt.data_ptr(), len(data))
+    assert ms[1].finish() == [5000] + [0] * 8 and ms[1].how == 3
+    assert ms[0].finish() == [5000] + [0] * 8 and ms[0].how == 3
+
+
 def test_counts_two_in_flight(rj, oracle, W):
     progs = [rj.Program(rx) for rx in W.REGEXDNA_PATTERNS]
     data = W.fasta_stripped_numpy(20000).tobytes()

@@ -873,6 +873,67 @@ def test_multi_start_finish_two_in_flight():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["default", "mode4", "mode1", "tail_stream", "general"])
+def test_multi_finish_after_overflowed_regions(variant):
+    """rj_multi_finish after a run whose regions overflowed: the first attempt was enqueued by rj_multi_start, the larger
+    ones run inside rj_multi_finish.  Two objects in flight over a text made of hits only (every region overflows its first
+    capacity; in mode 4 the scan kernel's LDS slots) and a sparse one, each object seeing dense, sparse, dense: step by step
+    the counts, the return value and every pattern's spans of rj_multi_run on a fresh object; the first dense step of each
+    object reports its retries, the second one needs none."""
+    import torch
+    import rejit_amd
+    from rejit_amd import workloads as W
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream(dev).cuda_stream
+    if variant == "general":
+        patterns = [b"qwerty", b"zxcvbn", b"plmokn", b"ijbuhv"]
+        rng = random.Random(78)
+        sparse = bytearray(rng.choices(b"abcdefghijklmnopqrstuvwxyz 0123456789", k=30000))
+        for k in range(30):
+            sparse[1000 * k + 17:1000 * k + 23] = patterns[k % 4]
+        datas = [b"qwertyzxcvbnplmoknijbuhv" * 27000, bytes(sparse)]
+    else:
+        patterns = W.REGEXDNA_PATTERNS
+        datas = [b"agggtaaatttaccct" * 40000, W.fasta_stripped_numpy(30000).tobytes()]
+    progs = [rejit_amd.Program(rx) for rx in patterns]
+    texts = [torch.from_numpy(np.frombuffer(d + bytes(16), dtype=np.uint8).copy()).to(dev) for d in datas]
+
+    def make():
+        m = rejit_amd.MultiScan(progs)
+        if variant == "mode4":
+            m.set_mode(4)
+        elif variant == "mode1":
+            m.set_mode(1)
+        elif variant == "tail_stream":
+            m.set_tail_stream(True)
+        return m
+
+    want = []
+    for d, t in zip(datas, texts):
+        ref = make()                                                    # (a fresh object per text: its first capacities)
+        counts = ref.run(t.data_ptr(), len(d), stream=st)
+        want.append((counts, ref.how, [ref.scan(i).spans() for i in range(len(progs))]))
+    objs = [make(), make()]
+    order = [0, 0, 1, 1, 0, 0]                                          # step k: object k % 2 over text order[k]
+
+    def collect(k):
+        m = objs[k % 2]
+        got = (m.finish(), m.how, [m.scan(i).spans() for i in range(len(progs))])
+        assert got == want[order[k]], (variant, k)
+        retries = max(m.scan(i).stats()["retries"] for i in range(len(progs)))
+        if k < 2:
+            assert retries >= 1, (variant, k)                           # the path under test was taken
+        elif k >= 4:
+            assert retries == 0, (variant, k)                           # the same text again: the capacities hold
+
+    for k in range(len(order)):
+        objs[k % 2].start(texts[order[k]].data_ptr(), len(datas[order[k]]), stream=st)
+        if k >= 1:
+            collect(k - 1)
+    collect(len(order) - 1)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("variant", ["tails_on_own_streams", "stream_per_object"])
 def test_multi_two_in_flight_on_tail_streams(variant):
     """The two other ways to keep two steps in flight (bench.py's headline loop and its extras): every run's tails on a
