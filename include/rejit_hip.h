@@ -282,6 +282,38 @@ int64_t rj_scan_records_replace(rj_scan* scan, const void* d_text, uint64_t n, c
                                 const uint64_t* d_indices, uint64_t n_indices, const char* with, uint64_t with_len, int fill,
                                 uint64_t lead, uint64_t gap, void* d_out, uint64_t out_cap, uint64_t* d_out_begin,
                                 uint64_t* d_out_end, void* hip_stream);
+/* The FIELDS of records -- the pieces between a record's own matches: `awk -F RE`, `cut`, str.split, Arrow's
+ * split_pattern_regex -- or the MATCHES themselves per record (`grep -o`, str.findall), as a piece table: a record table over
+ * the same device text whose rows are the pieces, plus Arrow-style offsets that say which pieces belong to which row
+ * (rejit_amd/csrc/record_split.hip).  The text is not an argument, only its length n (for the row
+ * checks): the call reads tables and the scan's span list and nothing else.  k, r(j) and d_indices are those of
+ * rj_scan_records_pack: any order, repeats allowed, non-NULL with n_indices == 0 is no rows.  The match list is the list of the
+ * scan's last run, of length m; d_counts / d_first are what rj_scan_records wrote for THIS record table on that run.  Record
+ * r = r(j) is [rb, re), with f = first[r], c = count[r] and own matches (b_t, e_t) = spans[f + t], t < c:
+ *     RJ_SPLIT_BETWEEN: row j has c + 1 pieces, piece t = [t == 0 ? rb : e_{t-1}, t == c ? re : b_t)
+ *     RJ_SPLIT_MATCHES: row j has c pieces,     piece t = [b_t, e_t)          (a row without a match has none)
+ *     piece_first[0] = 0, piece_first[j + 1] = piece_first[j] + (pieces of row j), P = piece_first[k]
+ * The BETWEEN pieces are the parts of the record that rj_scan_records_replace copies as text: joining them with `with` gives
+ * exactly that call's R(r).  Empty pieces are pieces (two matches that touch, a match at the record's begin or end), and an
+ * empty match at p cuts at p.  d_piece_first: device, k + 1 uint64, may be NULL (the scan then keeps its own, as the pack does
+ * with its begins).  Row j's pieces are rows piece_first[j] .. piece_first[j + 1] of d_piece_begin / d_piece_end (device,
+ * piece_cap uint64 each), as offsets into the text.  Returns P WHATEVER piece_cap is and never writes a piece row at or beyond
+ * piece_cap; d_piece_begin == d_piece_end == NULL with piece_cap == 0 is the size query (d_piece_first is still written when
+ * given).  With P <= piece_cap every row of the three tables is written exactly once, nothing has to be cleared first.  The
+ * scan lends scratch only: spans, stats and the state of its last rj_scan_records (rj_scan_records_select included) stay as
+ * they were.  Without d_indices both tables are ascending and not overlapping: valid record tables for rj_scan_records (a
+ * second pattern per field), and rj_scan_records_pack over them prints the fields or the matches.
+ * Refusals (RJ_BAD_ARGUMENT; one that names a row gives the first bad j as "row <j> "; a refused call writes no piece row and
+ * is never led outside the list or the tables): for both values of `what` the six of rj_scan_records_replace -- a bad index; a
+ * bad row (begin <= end <= n); count[r] == UINT32_MAX; first[r] + count[r] > m; a first match that begins before rec_begin[r];
+ * a last match that ends beyond rec_end[r] (the records are not independent: rj_scan_records_pack with the separator makes
+ * them so) --; a null argument; d_counts or d_first NULL while k > 0; a table that is not 8-byte aligned (d_counts: 4-byte);
+ * `what` outside {0, 1}; a last run that left no list (counts-only); k >= 2^60, or k * (m + 1) >= 2^62. */
+enum { RJ_SPLIT_BETWEEN = 0, RJ_SPLIT_MATCHES = 1 };
+int64_t rj_scan_records_split(rj_scan* scan, uint64_t n, const uint64_t* d_rec_begin, const uint64_t* d_rec_end,
+                              uint64_t n_records, const uint32_t* d_counts, const uint64_t* d_first,
+                              const uint64_t* d_indices, uint64_t n_indices, int what, uint64_t* d_piece_first,
+                              uint64_t* d_piece_begin, uint64_t* d_piece_end, uint64_t piece_cap, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_split.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -195,7 +195,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split"]
 
 
 def load_library():
@@ -301,6 +301,8 @@ def load_library():
     L.rj_scan_records_pack.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
     L.rj_scan_records_replace.restype = i64
     L.rj_scan_records_replace.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, cp, u64, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
+    L.rj_scan_records_split.restype = i64
+    L.rj_scan_records_split.argtypes = [vp, u64, vp, vp, u64, vp, vp, vp, u64, ctypes.c_int, vp, vp, vp, u64, vp]
     _lib = L
     return L
 
@@ -711,6 +713,47 @@ class Scan:
         if total > out.numel():
             raise RejitError(-4, "replace_records: the new text has %d bytes, `out` %d" % (total, out.numel()))
         return out[:total], out_begin, out_end
+
+    def split_records(self, rec_begin, rec_end, result: RecordsResult, n: int, indices=None, what: str = "between", stream=None):
+        """rj_scan_records_split: the fields (what="between": the pieces between a record's own matches -- `awk -F RE`,
+        str.split) or the matches themselves (what="matches": `grep -o`, str.findall) of the records [rec_begin[i],
+        rec_end[i]) of a text of n bytes -- all of them, or those `indices` names, as pack_records' -- as a piece table over
+        the same text.  `result` is the RecordsResult of the run_records that produced the scan's current list.  Returns
+        (piece_begin, piece_end, piece_first): int64 device tensors; row j's pieces are rows piece_first[j] ..
+        piece_first[j + 1] of the first two (offsets into the text), piece_first has k + 1 entries.  ONE size query (the plan
+        alone), exactly P rows allocated, one call.  Without indices (piece_begin, piece_end) is a valid record table for
+        run_records and pack_records.  RejitError (RJ_BAD_ARGUMENT, naming the first bad row) as replace_records."""
+        import torch
+
+        n_records = int(rec_begin.numel())
+        device = rec_begin.device
+        for x in (rec_begin, rec_end, result.first):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == device and x.numel() == n_records
+        assert result.counts.dtype == torch.int32 and result.counts.is_contiguous() and result.counts.device == device and result.counts.numel() == n_records
+        if what not in ("between", "matches"):
+            raise ValueError("split_records: what is 'between' or 'matches', not %r" % (what,))
+        code = 0 if what == "between" else 1
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=device)   # (a non-null pointer: NULL means every record)
+        else:
+            k = n_records
+        st = torch.cuda.current_stream(device).cuda_stream if stream is None else stream
+        piece_first = torch.empty(k + 1, dtype=torch.int64, device=device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+
+        def call(pb, pe, cap):
+            return int(_check(self._lib.rj_scan_records_split(self._h, int(n), ptr(rec_begin), ptr(rec_end), n_records, ptr(result.counts),
+                                                              ptr(result.first), ptr(indices), k, code, ptr(piece_first), ptr(pb) if cap else None,
+                                                              ptr(pe) if cap else None, cap, ctypes.c_void_p(st))))
+        total = call(None, None, 0)
+        piece_begin = torch.empty(total, dtype=torch.int64, device=device)
+        piece_end = torch.empty(total, dtype=torch.int64, device=device)
+        if total:
+            call(piece_begin, piece_end, total)
+        return piece_begin, piece_end, piece_first
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""

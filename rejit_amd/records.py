@@ -68,3 +68,34 @@ def all_relative_spans(spans, result, rec_begin) -> List[List[Tuple[int, int]]]:
     for f, c, b in zip(result.first.cpu().tolist(), result.counts.cpu().tolist(), rec_begin.cpu().tolist()):
         out.append([(x - b, y - b) for x, y in sp[f:f + (c & 0xFFFFFFFF)]])
     return out
+
+
+def field_records(piece_begin, piece_end, piece_first, f: int):
+    """(begin, end, present): field f (0-based; negative: counted from the row's end) of every row of a piece table
+    (Scan.split_records) as a record table -- int64 tensors of k rows -- and a bool tensor that says which rows have such a
+    field.  A row with fewer fields gets the empty record at its last piece's end (a row without any piece, and a table
+    without pieces: the empty record at 0)."""
+    import torch
+
+    lo, hi = piece_first[:-1], piece_first[1:]
+    at = lo + f if f >= 0 else hi + f
+    present = (at >= lo) & (at < hi)
+    n_pieces = int(piece_begin.numel())
+    if n_pieces == 0:
+        zero = torch.zeros_like(lo)
+        return zero, zero.clone(), present
+    last = (hi - 1).clamp(min=0)
+    has_any = hi > lo
+    fallback = torch.where(has_any, piece_end[last], torch.zeros_like(lo))
+    pick = torch.where(present, at, torch.zeros_like(at))
+    begin = torch.where(present, piece_begin[pick], fallback)
+    end = torch.where(present, piece_end[pick], fallback)
+    return begin.contiguous(), end.contiguous(), present
+
+
+def nonempty_pieces(piece_begin, piece_end):
+    """The indices (int64, ascending) of the pieces with end > begin: with Scan.pack_records over the piece table, the
+    fields or matches that have bytes."""
+    import torch
+
+    return torch.nonzero(piece_end > piece_begin).reshape(-1).contiguous()

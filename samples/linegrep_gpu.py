@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -14,6 +14,11 @@ answer on the GPU:
   -v   select the lines WITHOUT a match
   -s WITH   print every line -- with -p / -v: every selected line -- with its matches replaced by WITH (rj_scan_records_replace:
        the new text is made on the device and is the only download): `sed -E 's/PATTERN/WITH/g'`, respectively `grep ... | sed ...`
+  -o   print every non-empty match of every line -- with -p / -v: of every selected line -- on a line of its own (`grep -E -o`):
+       rj_scan_records_split lists the matches per line as a piece table, rj_scan_records_pack gathers the non-empty ones
+  -f N   PATTERN is the field separator: print field N (1-based) of every line -- with -p / -v: of every selected line --, an
+       empty line where a line has fewer fields (`awk -F PATTERN '{print $N}'`): the fields are rj_scan_records_split's pieces
+       between the matches, field N of every row a torch gather over its offsets, the packed fields the only download
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -30,9 +35,15 @@ def main(argv):
     if "-s" in argv[:-1]:
         at = argv.index("-s")
         repl, argv = os.fsencode(argv[at + 1]), argv[:at] + argv[at + 2:]
+    field = None
+    if "-f" in argv[:-1]:
+        at = argv.index("-f")
+        field, argv = argv[at + 1], argv[:at] + argv[at + 2:]
+    matches_out = "-o" in argv
+    argv = [a for a in argv if a != "-o"]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
-    if len(rest) != 2:
+    if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)):
         sys.stderr.write(__doc__)
         return 2
     path, pattern = rest
@@ -50,7 +61,7 @@ def main(argv):
     rejit_amd.build()
     data = np.fromfile(path, dtype=np.uint8)
     if data.size == 0:
-        if not numbers and not lines_out and repl is None:
+        if not numbers and not lines_out and repl is None and not matches_out and field is None:
             print(0)
         return 1
     text = torch.from_numpy(data).to("cuda:0")                       # the only upload
@@ -70,6 +81,21 @@ def main(argv):
             sys.stdout.flush()
             sys.stdout.buffer.write(new.cpu().numpy().tobytes())     # the only download besides the summary
         return 0 if every or selected else 1
+    if matches_out or field is not None:
+        every = not invert and "-p" not in flags
+        lines = None if every else scan.select_records(invert=invert)
+        if every or selected:
+            pb, pe, pf = scan.split_records(begins, ends, result, int(text.numel()), indices=lines, what="matches" if matches_out else "between")
+            if matches_out:
+                keep = records.nonempty_pieces(pb, pe)
+            else:
+                pb, pe, _ = records.field_records(pb, pe, pf, int(field) - 1)
+                keep = None
+            if keep is None or keep.numel():
+                packed, _, _ = scan.pack_records(text, pb, pe, indices=keep, fill=10, lead=0, gap=1)
+                sys.stdout.flush()
+                sys.stdout.buffer.write(packed.cpu().numpy().tobytes())   # the only download besides the summary
+        return 0 if selected or (every and field is not None) else 1
     if numbers:
         lines = scan.select_records(invert=invert)                   # the only download besides the summary
         sys.stdout.write("".join("%d\n" % (i + 1) for i in lines.cpu().tolist()))
