@@ -166,7 +166,8 @@ def test_overlapping_pairs_are_resolved_in_the_kernel(rj, oracle, W):
     rng = random.Random(13)
     # (5 MB: 2442 blocks over the 1024 waves of a 256-workgroup grid -- the first waves own three blocks each, so the block
     # boundaries at 2048 and 4096 lie INSIDE wave 0's span and the one at 6144 between two spans.  Texts below 2 MiB give
-    # every wave one block: every block boundary is a span boundary there, see the next test.)
+    # every wave one block: every block boundary is a span boundary there, see the next test.  Spans of 2 .. 17 blocks on
+    # small texts under a forced grid: tests/test_gpu_seams.py.)
     n = 5000000
     base = bytearray(np.random.default_rng(13).choice(np.frombuffer(b"acgt", dtype=np.uint8), n).tobytes())
     overlap = b"agggtaaagggtaaa"
