@@ -278,17 +278,18 @@ class Case:
         return "+".join(tags), start - seam
 
 
-def plant_text(n, seams, strings, bg, cover, rot, only=None, keep_clear=(), no_cross=()):
+def plant_text(n, seams, strings, bg, cover, rot, only=None, keep_clear=(), no_cross=(), rare=None, text=None, placed=None):
     """One string at every seam that has room: (text, [(start, string, tags, seam)]).  The (length, offset) pair of a seam is
     the one its classes have seen least so far (`cover`), so the offsets rotate over the seams of a text and over the texts
-    of a family; which of two seams closer than a plant + MIN_GAP is served first rotates with `rot`."""
-    text = bytearray([bg]) * n
+    of a family; which of two seams closer than a plant + MIN_GAP is served first rotates with `rot`.  `rare` ranks other
+    seam classes than this module's (tests/window_sweep.py); `text` and `placed` continue an earlier call's text."""
+    text = bytearray([bg]) * n if text is None else text
     by_len = {}
     for s in strings:
         by_len.setdefault(len(s), []).append(s)
-    rare = {"OWN": 0, "SG": 0, "GE": 0, "GF": 0, "GG": 0, "BH1": 0, "BH2": 0, "SW": 1, "B01": 2, "B12": 2, "P": 3 + rot % 2, "LA": 3 + (rot + 1) % 2, "LB": 3 + (rot + 1) % 2}
+    rare = rare if rare is not None else {"OWN": 0, "SG": 0, "GE": 0, "GF": 0, "GG": 0, "BH1": 0, "BH2": 0, "SW": 1, "B01": 2, "B12": 2, "P": 3 + rot % 2, "LA": 3 + (rot + 1) % 2, "LB": 3 + (rot + 1) % 2}
     order = sorted(range(len(seams)), key=lambda i: (min(rare[t] for t in seams[i][1]), seams[i][0]))
-    placed = []   # sorted (start, end)
+    placed = [] if placed is None else placed   # sorted (start, end)
     out = []
     for i in order:
         pos, tags = seams[i]

@@ -363,6 +363,7 @@ int pe_plan(const char* re, uint64_t* info, uint32_t* window_values) {
   info[11] = P.behind;
   info[9] = P.float_min;
   info[10] = P.float_max;
+  info[12] = P.windows.empty() ? 0 : P.windows[0].len;
   for (size_t i = 0; i < P.windows.size(); i++) {
     window_values[4 * i] = P.windows[i].value0;
     window_values[4 * i + 1] = P.windows[i].mask0;
