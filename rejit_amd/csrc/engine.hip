@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "plane_args.h"
 #include "table_layout.h"
 
 using namespace rejit_amd;
@@ -245,6 +246,20 @@ int ensure_lists(rj_scan* s, uint32_t n_regions, uint32_t region_cap, uint64_t c
 
 namespace {
 
+#define RJ_TRY(call) do { const int rc_ = (call); if (rc_ != RJ_OK) return rc_; } while (0)
+
+int synchronise(hipStream_t st) {
+  RJ_HIP(hipStreamSynchronize(st));
+  RJ_HIP(hipGetLastError());
+  return RJ_OK;
+}
+
+// the counters of the kernels enqueued so far, in s->host_counters
+int read_counters(rj_scan* s, hipStream_t st) {
+  RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  return synchronise(st);
+}
+
 // Large path: more hit slots than finalize_small handles in LDS.  The slots are already in
 // text order, so no sort: drop the kNoMatch slots, then check / select.
 hipError_t prefix_scan(rj_scan* s, uint64_t* in, uint64_t* out, uint64_t count, bool is_max, hipStream_t st) {
@@ -260,6 +275,23 @@ hipError_t prefix_scan(rj_scan* s, uint64_t* in, uint64_t* out, uint64_t count, 
 
 int check_and_select(rj_scan* s, uint64_t n_upper, const FinalizeParams& fp, hipStream_t st);
 
+// keys_out / vals_out (nc candidates, begins below text_len) sorted by begin, through cand_begin / cand_end as the sort's output
+int sort_by_begin(rj_scan* s, uint64_t nc, uint64_t text_len, hipStream_t st) {
+  unsigned bits = 1;
+  while (bits < 64 && (text_len >> bits) != 0) bits++;
+  RJ_HIP(s->cand_begin.reserve(nc * sizeof(uint64_t)));
+  RJ_HIP(s->cand_end.reserve(nc * sizeof(uint64_t)));
+  uint64_t *keys = s->keys_out.as<uint64_t>(), *vals = s->vals_out.as<uint64_t>();
+  uint64_t *k2 = s->cand_begin.as<uint64_t>(), *v2 = s->cand_end.as<uint64_t>();
+  size_t tmp_bytes = 0;
+  RJ_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, k2, vals, v2, nc, 0, bits, st));
+  RJ_HIP(s->sort_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+  RJ_HIP(rocprim::radix_sort_pairs(s->sort_tmp.p, tmp_bytes, keys, k2, vals, v2, nc, 0, bits, st));
+  RJ_HIP(hipMemcpyAsync(keys, k2, nc * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  RJ_HIP(hipMemcpyAsync(vals, v2, nc * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  return RJ_OK;
+}
+
 int finalize_large(rj_scan* s, uint64_t n_slots, bool unsorted, uint64_t text_len, const FinalizeParams& fp, hipStream_t st) {
   s->stats.large_path = 1;
   RJ_HIP(s->keys_out.reserve(n_slots * sizeof(uint64_t)));
@@ -270,12 +302,9 @@ int finalize_large(rj_scan* s, uint64_t n_slots, bool unsorted, uint64_t text_le
   uint64_t* vals = s->vals_out.as<uint64_t>();
   uint64_t* sa = s->scan_a.as<uint64_t>();
   uint64_t* sb = s->scan_b.as<uint64_t>();
-  auto scan = [&](uint64_t* in, uint64_t* out, uint64_t count, bool is_max) -> hipError_t {
-    return prefix_scan(s, in, out, count, is_max, st);
-  };
   // 1. ordered compaction of the verified candidates
   launch_mark_valid(s->cand_end.as<uint64_t>(), n_slots, sa, st);
-  RJ_HIP(scan(sa, sb, n_slots, false));
+  RJ_HIP(prefix_scan(s, sa, sb, n_slots, false, st));
   launch_compact_valid(s->cand_begin.as<uint64_t>(), s->cand_end.as<uint64_t>(), sa, sb, n_slots, keys, vals,
                        s->counters.as<unsigned long long>(), st);
   if (unsorted) {
@@ -284,18 +313,7 @@ int finalize_large(rj_scan* s, uint64_t n_slots, bool unsorted, uint64_t text_le
     RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     RJ_HIP(hipStreamSynchronize(st));
     const uint64_t nc = s->host_counters[kCntCands];
-    if (nc > 1) {
-      unsigned bits = 1;
-      while (bits < 64 && (text_len >> bits) != 0) bits++;
-      uint64_t* k2 = s->cand_begin.as<uint64_t>();  // free again: reuse as sort output
-      uint64_t* v2 = s->cand_end.as<uint64_t>();
-      size_t tmp_bytes = 0;
-      RJ_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, k2, vals, v2, nc, 0, bits, st));
-      RJ_HIP(s->sort_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
-      RJ_HIP(rocprim::radix_sort_pairs(s->sort_tmp.p, tmp_bytes, keys, k2, vals, v2, nc, 0, bits, st));
-      RJ_HIP(hipMemcpyAsync(keys, k2, nc * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-      RJ_HIP(hipMemcpyAsync(vals, v2, nc * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    }
+    if (nc > 1) RJ_TRY(sort_by_begin(s, nc, text_len, st));  // (cand_begin / cand_end are free again)
   }
   return check_and_select(s, n_slots, fp, st);
 }
@@ -308,9 +326,7 @@ int check_and_select(rj_scan* s, uint64_t n_slots, const FinalizeParams& fp, hip
   if (fp.detect_adjacent) launch_detect_adjacent(keys, vals, n_slots, s->counters.as<unsigned long long>(), st);
   launch_check_and_interleave(keys, vals, s->counters.as<unsigned long long>() + kCntCands, n_slots, fp.carry_cur,
                               s->out.as<uint64_t>(), s->out_cap, s->counters.as<unsigned long long>() + kCntUnordered, st);
-  RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  RJ_HIP(hipStreamSynchronize(st));
-  RJ_HIP(hipGetLastError());
+  RJ_TRY(read_counters(s, st));
   return resolve_selection(s, fp, st);
 }
 
@@ -350,9 +366,7 @@ int resolve_selection(rj_scan* s, const FinalizeParams& fp, hipStream_t st) {
     RJ_HIP(hipMemcpyAsync(s->counters.as<unsigned long long>() + kCntHits, scratch, sizeof(unsigned long long),
                           hipMemcpyHostToDevice, st));
     launch_finalize_small(f, st);
-    RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    RJ_HIP(hipStreamSynchronize(st));
-    RJ_HIP(hipGetLastError());
+    RJ_TRY(read_counters(s, st));
     s->result_count = s->host_counters[kCntFinal];
     return RJ_OK;
   }
@@ -362,9 +376,6 @@ int resolve_selection(rj_scan* s, const FinalizeParams& fp, hipStream_t st) {
   RJ_HIP(s->cand_begin.reserve(n_cands * sizeof(uint64_t)));
   uint64_t* sa = s->scan_a.as<uint64_t>();
   uint64_t* sb = s->scan_b.as<uint64_t>();
-  auto scan = [&](uint64_t* in, uint64_t* out, uint64_t count, bool is_max) -> hipError_t {
-    return prefix_scan(s, in, out, count, is_max, st);
-  };
   //   pmax  = exclusive prefix max of the ends            (sa)
   //   taken = per-cluster sequential walk                  (taken)
   //   last  = exclusive prefix max of (taken ? i+1 : 0)    (sb; cand_begin reused as scratch)
@@ -372,18 +383,16 @@ int resolve_selection(rj_scan* s, const FinalizeParams& fp, hipStream_t st) {
   //   pos   = exclusive prefix sum of keep                 (sb)
   RJ_HIP(s->taken.reserve(n_cands));
   uint64_t* scratch = s->cand_begin.as<uint64_t>();
-  RJ_HIP(scan(vals, sa, n_cands, true));
+  RJ_HIP(prefix_scan(s, vals, sa, n_cands, true, st));
   RJ_HIP(s->chain_blocks.reserve(chain_select_scratch_bytes(n_cands)));
   launch_chain_select(keys, vals, sa, n_cands, fp.carry_cur, s->taken.as<uint8_t>(), sb, scratch, s->chain_blocks.as<uint64_t>(), st);
   launch_taken_index(s->taken.as<uint8_t>(), n_cands, scratch, st);
-  RJ_HIP(scan(scratch, sb, n_cands, true));
+  RJ_HIP(prefix_scan(s, scratch, sb, n_cands, true, st));
   launch_zero_length_rule(keys, vals, s->taken.as<uint8_t>(), sb, n_cands, fp.carry_prev_end, fp.have_prev, sa,
                           fp.detect_conflict ? s->counters.as<unsigned long long>() + kCntConflict : nullptr, st);
-  RJ_HIP(scan(sa, sb, n_cands, false));
+  RJ_HIP(prefix_scan(s, sa, sb, n_cands, false, st));
   launch_compact_kept(keys, vals, sa, sb, n_cands, s->out.as<uint64_t>(), s->out_cap, s->counters.as<unsigned long long>(), st);
-  RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  RJ_HIP(hipStreamSynchronize(st));
-  RJ_HIP(hipGetLastError());
+  RJ_TRY(read_counters(s, st));
   s->result_count = s->host_counters[kCntFinal];
   return RJ_OK;
 }
@@ -430,6 +439,43 @@ WindowSet make_window_set(const rj_program* rp) {
   return ws;
 }
 
+// ---- what the one-pass routes below (assertions, streams, runs, pairs) share, and run_range with them
+// room for `cap` pairs in s->out (grow-only, the contents are not kept)
+static int grow_out(rj_scan* s, uint64_t cap) {
+  if (cap > s->out_cap) {
+    RJ_HIP(s->out.reserve(cap * 2 * sizeof(uint64_t)));
+    s->out_cap = cap;
+  }
+  return RJ_OK;
+}
+
+// the device counters, and the pinned ones a route's kernels write themselves (kCntOverrun: the routes that can void a run)
+static int clear_counters(rj_scan* s, bool overrun, hipStream_t st) {
+  RJ_HIP(hipMemsetAsync(s->counters.p, 0, kCntSize * sizeof(unsigned long long), st));
+  if (overrun) s->host_counters[kCntOverrun] = 0;
+  s->host_counters[kCntFinal] = 0;
+  return RJ_OK;
+}
+
+// rj_stats.scan_ms: from the scan kernel's start to the end event of the pass that has just been synchronised
+static void add_scan_ms(rj_scan* s) {
+  float ms = 0.f;
+  if (s->timing) (void)hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
+  s->stats.scan_ms += ms;
+}
+
+// A route's finished answer: cnt pairs at `result` (nullptr: a count-only run leaves no list), the next run's hint, the
+// stats and the flag of the path that answered.  Returns the routes' 1 = done.
+static int accept_answer(rj_scan* s, uint64_t cnt, const uint64_t* result, int32_t rj_stats::*path = nullptr, int32_t how = 1) {
+  s->result_count = cnt;
+  s->result = result;
+  s->hits_hint = cnt;
+  s->stats.n_hits += cnt;
+  s->stats.n_candidates += cnt;
+  if (path != nullptr) s->stats.*path = how;
+  return 1;
+}
+
 // Assertion-only patterns (`^`, `$`: the line table of a grep-like caller) from the beginning of a selection: every
 // position in a matching context is a match, so the result is written once, in place (emit_scan.hip).
 // 1 = done, 0 = not applicable / the prefix scan timed out (the caller takes the dense kernel), < 0 = error.
@@ -440,20 +486,12 @@ static int run_assertions(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_
   uint64_t cap = std::max<uint64_t>(s->hits_hint + s->hits_hint / 8 + 1024, (se - sb) / 48 + 1024);
   RJ_HIP(s->scan_a.reserve(emit_scratch_bytes(sb, se)));
   for (int attempt = 0; attempt < 3; attempt++) {
-    if (cap > s->out_cap) {
-      RJ_HIP(s->out.reserve(cap * 2 * sizeof(uint64_t)));
-      s->out_cap = cap;
-    }
-    RJ_HIP(hipMemsetAsync(s->counters.p, 0, kCntSize * sizeof(unsigned long long), st));
-    s->host_counters[kCntOverrun] = 0;
-    s->host_counters[kCntFinal] = 0;
+    RJ_TRY(grow_out(s, cap));
+    RJ_TRY(clear_counters(s, true, st));
     launch_emit_assertions(d_text, n, sb, se, D.nullable, s->scan_a.as<unsigned long long>(), s->out.as<uint64_t>(), s->out_cap,
                            s->counters.as<unsigned long long>(), s->host_counters, s->t0(), s->ev[2], st);
-    RJ_HIP(hipStreamSynchronize(st));
-    RJ_HIP(hipGetLastError());
-    float ms = 0.f;
-    if (s->timing) (void)hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
-    s->stats.scan_ms += ms;
+    RJ_TRY(synchronise(st));
+    add_scan_ms(s);
     if (s->host_counters[kCntOverrun] != 0) return 0;
     const uint64_t cnt = s->host_counters[kCntFinal];
     if (cnt > s->out_cap) {  // more matches than room: once more with room for all of them
@@ -461,12 +499,7 @@ static int run_assertions(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_
       cap = cnt + cnt / 16 + 1024;
       continue;
     }
-    s->result_count = cnt;
-    s->result = s->out.as<uint64_t>();
-    s->hits_hint = cnt;
-    s->stats.n_hits += cnt;
-    s->stats.n_candidates += cnt;
-    return 1;
+    return accept_answer(s, cnt, s->out.as<uint64_t>());
   }
   return 0;
 }
@@ -494,27 +527,18 @@ static int run_streams(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t s
   uint64_t cap = std::max<uint64_t>(s->hits_hint + s->hits_hint / 8 + 1024, (se - sb) / 64 + 1024);
   RJ_HIP(s->scan_a.reserve(stream_scratch_bytes(a.n_tiles)));
   for (int attempt = 0; attempt < 3; attempt++) {
-    if (cap > s->out_cap) {
-      RJ_HIP(s->out.reserve(cap * 2 * sizeof(uint64_t)));
-      s->out_cap = cap;
-    }
-    RJ_HIP(hipMemsetAsync(s->counters.p, 0, kCntSize * sizeof(unsigned long long), st));
-    s->host_counters[kCntOverrun] = 0;
-    s->host_counters[kCntFinal] = 0;
+    RJ_TRY(grow_out(s, cap));
+    RJ_TRY(clear_counters(s, true, st));
     a.out = s->out.as<uint64_t>();
     a.out_cap = s->out_cap;
     a.counters = s->counters.as<unsigned long long>();
     a.host_counters = s->host_counters;
     launch_dense_streams(a, s->scan_a.as<unsigned long long>(), s->t0(), s->ev[2], st);
-    unsigned long long slow = 0;
     RJ_HIP(hipMemcpyAsync(&s->host_counters[kCntSlowStarts], s->counters.as<unsigned long long>() + kCntSlowStarts, sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, st));
-    RJ_HIP(hipStreamSynchronize(st));
-    RJ_HIP(hipGetLastError());
-    slow = s->host_counters[kCntSlowStarts];
-    float ms = 0.f;
-    if (s->timing) (void)hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
-    s->stats.scan_ms += ms;
+    RJ_TRY(synchronise(st));
+    const unsigned long long slow = s->host_counters[kCntSlowStarts];
+    add_scan_ms(s);
     if (s->host_counters[kCntOverrun] != 0) {
       s->streams_off = true;  // (a long-lived thread or a time-out: this text is not for the register steps)
       s->stats.retries++;
@@ -533,16 +557,52 @@ static int run_streams(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t s
       cap = cnt + cnt / 16 + 1024;
       continue;
     }
-    s->result_count = cnt;
-    s->result = s->out.as<uint64_t>();
-    s->hits_hint = cnt;
-    s->stats.n_hits += cnt;
-    s->stats.n_candidates += cnt;
-    s->stats.stream_path = 1;
     s->stats.slow_starts = static_cast<int32_t>(std::min<unsigned long long>(slow, 0x7fffffffull));
-    return 1;
+    return accept_answer(s, cnt, s->out.as<uint64_t>(), &rj_stats::stream_path);
   }
   return 0;
+}
+
+// RunParams of the matches that begin in [sb, se) and are looked for from min_start on, over the scan's own buffers.
+static int run_params(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, uint64_t min_start, RunParams* a) {
+  a->text = d_text;
+  a->n = n;
+  a->sb = sb;
+  a->se = se;
+  a->min_start = min_start;
+  a->plan = s->prog->run;
+  a->tile_bytes = run_tile_bytes(n - std::min<uint64_t>(min_start, n));
+  a->n_tiles = run_tiles(min_start, n, a->tile_bytes, &a->first_tile);
+  RJ_HIP(s->run_summaries.reserve(sizeof(RunSummary) * run_resolve_slots(a->n_tiles)));
+  RJ_HIP(s->run_tile_in.reserve(sizeof(RunTileIn) * run_resolve_slots(a->n_tiles)));
+  a->summaries = s->run_summaries.as<RunSummary>();
+  a->tile_in = s->run_tile_in.as<RunTileIn>();
+  a->counters = s->counters.as<unsigned long long>();
+  a->host_counters = s->host_counters;
+  a->out = s->out.as<uint64_t>();
+  a->out_cap = s->out_cap;
+  return RJ_OK;
+}
+
+// The run kernels or, pair, the pair kernels (run_scan.hip: the same three steps over the same buffers): summary, resolve,
+// and -- once the number of pairs has sized the output -- emit.  count_only: the run ends behind the resolve, with the count
+// and no list (and no scan_ms: the emit's end event is not recorded).
+static int run_three_steps(rj_scan* s, RunParams& a, bool pair, bool count_only, hipStream_t st) {
+  const int32_t path = pair ? 2 : 1;  // rj_stats.run_path
+  RJ_TRY(clear_counters(s, false, st));
+  (pair ? launch_pair_summary : launch_run_summary)(a, s->t0(), nullptr, st);
+  (pair ? launch_pair_resolve : launch_run_resolve)(a, st);
+  RJ_TRY(synchronise(st));  // (the number of pairs sizes the output)
+  const uint64_t cnt = s->host_counters[kCntFinal];
+  if (count_only) return accept_answer(s, cnt, nullptr, &rj_stats::run_path, path);
+  if (cnt > s->out_cap) RJ_TRY(grow_out(s, cnt + cnt / 16 + 1024));
+  a.out = s->out.as<uint64_t>();
+  a.out_cap = s->out_cap;
+  if (cnt) (pair ? launch_pair_emit : launch_run_emit)(a, s->ev[2], st);
+  else RJ_HIP(hipEventRecord(s->ev[2], st));
+  RJ_TRY(synchronise(st));
+  add_scan_ms(s);  // (first pass's start to the second pass's end, the scan between them included)
+  return accept_answer(s, cnt, s->out.as<uint64_t>(), &rj_stats::run_path, path);
 }
 
 // Patterns with one long-lived thread in one loop position (run_scan.h: `X+`, `A L*`, `A L* B`, `X+ B`): two passes over
@@ -553,15 +613,7 @@ static int run_runs(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, 
                     hipStream_t st) {
   const rj_program* rp = s->prog;
   if (!rp->run.ok || se <= sb) return 0;
-  RunParams a{};
-  a.text = d_text;
-  a.n = n;
-  // (`A L+` plans: the kernels' starts are the marks one byte behind a match's begin -- the three positions move with them)
-  const uint64_t lag = rp->run.lag;
-  a.sb = sb + lag;
-  a.se = std::min<uint64_t>(se, n) + lag;   // (a match consumes at least one byte: none begins at n)
-  a.min_start = std::max<uint64_t>(sb, have_prev ? carry_cur : 0) + lag;
-  a.plan = rp->run;
+  uint32_t blocked_in = 0;
   if (have_prev && rp->run.has_b && carry_prev_end >= 1 && carry_prev_end <= n) {
     // the carried-in match ended behind its B at carry_prev_end - 1: when that byte is no break, the segment goes on and has
     // had its match (run_scan.h)
@@ -570,150 +622,88 @@ static int run_runs(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, 
     RJ_HIP(hipStreamSynchronize(st));
     const Program& P = *rp->host;
     const int l_pos = P.n_pos == 3 ? 1 : 0;
-    a.blocked_in = ((P.cls[last] >> l_pos) & 1u) ? 1u : 0u;
+    blocked_in = ((P.cls[last] >> l_pos) & 1u) ? 1u : 0u;
   }
-  a.tile_bytes = run_tile_bytes(n - std::min<uint64_t>(a.min_start, n));
-  a.n_tiles = run_tiles(a.min_start, n, a.tile_bytes, &a.first_tile);
-  RJ_HIP(s->run_summaries.reserve(sizeof(RunSummary) * run_resolve_slots(a.n_tiles)));
-  RJ_HIP(s->run_tile_in.reserve(sizeof(RunTileIn) * run_resolve_slots(a.n_tiles)));
-  a.summaries = s->run_summaries.as<RunSummary>();
-  a.tile_in = s->run_tile_in.as<RunTileIn>();
-  a.counters = s->counters.as<unsigned long long>();
-  a.host_counters = s->host_counters;
-  a.out = s->out.as<uint64_t>();
-  a.out_cap = s->out_cap;
-  RJ_HIP(hipMemsetAsync(s->counters.p, 0, kCntSize * sizeof(unsigned long long), st));
-  s->host_counters[kCntFinal] = 0;
-  launch_run_summary(a, s->t0(), nullptr, st);
-  launch_run_resolve(a, st);
-  RJ_HIP(hipStreamSynchronize(st));   // (the number of pairs sizes the output)
-  RJ_HIP(hipGetLastError());
-  const uint64_t cnt = s->host_counters[kCntFinal];
+  // (`A L+` plans: the kernels' starts are the marks one byte behind a match's begin -- the three positions move with them)
+  const uint64_t lag = rp->run.lag;
+  RunParams a{};
+  // (a match consumes at least one byte: none begins at n)
+  RJ_TRY(run_params(s, d_text, n, sb + lag, std::min<uint64_t>(se, n) + lag, std::max<uint64_t>(sb, have_prev ? carry_cur : 0) + lag, &a));
+  a.blocked_in = blocked_in;
   // (`^` in front of the shape is a mask on the kernels' start stream, `$` behind it a test of the closing break: run_scan.hip)
-  if (s->count_only_run && sb == 0 && se > n) {   // MatchAllCount of the whole text: one pass over it
-    s->result_count = cnt;
-    s->result = nullptr;
-    s->hits_hint = cnt;
-    s->stats.n_hits += cnt;
-    s->stats.n_candidates += cnt;
-    s->stats.run_path = 1;
-    return 1;
-  }
-  if (cnt > s->out_cap) {
-    const uint64_t cap = cnt + cnt / 16 + 1024;
-    RJ_HIP(s->out.reserve(cap * 2 * sizeof(uint64_t)));
-    s->out_cap = cap;
-  }
-  a.out = s->out.as<uint64_t>();
-  a.out_cap = s->out_cap;
-  if (cnt) launch_run_emit(a, s->ev[2], st);
-  else RJ_HIP(hipEventRecord(s->ev[2], st));
-  RJ_HIP(hipStreamSynchronize(st));
-  RJ_HIP(hipGetLastError());
-  float ms = 0.f;
-  if (s->timing) (void)hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
-  s->stats.scan_ms += ms;   // (first pass's start to the second pass's end, the scan between them included)
-  s->result_count = cnt;
-  s->result = s->out.as<uint64_t>();
-  s->hits_hint = cnt;
-  s->stats.n_hits += cnt;
-  s->stats.n_candidates += cnt;
-  s->stats.run_path = 1;
-  return 1;
+  // MatchAllCount of the whole text: one pass over it
+  return run_three_steps(s, a, false, s->count_only_run && sb == 0 && se > n, st);
 }
 
 // The PAIR shape (run_scan.h: `"[^"]*"`, `'[^'\n]*'`): the same three steps with the pair kernels -- whole texts without a
 // carried-in state only (what crosses a cut is the parity of the Q bytes since the last reset, which a shard does not know).
 // 1 = done, 0 = not this path, < 0 = error.
 static int run_pairs(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, hipStream_t st) {
-  const rj_program* rp = s->prog;
-  if (!rp->run.pair || sb != 0 || se < n || n == 0) return 0;
+  if (!s->prog->run.pair || sb != 0 || se < n || n == 0) return 0;
   RunParams a{};
-  a.text = d_text;
-  a.n = n;
-  a.sb = 0;
-  a.se = n;
-  a.plan = rp->run;
-  a.tile_bytes = run_tile_bytes(n);
-  a.n_tiles = run_tiles(0, n, a.tile_bytes, &a.first_tile);
-  RJ_HIP(s->run_summaries.reserve(sizeof(RunSummary) * run_resolve_slots(a.n_tiles)));
-  RJ_HIP(s->run_tile_in.reserve(sizeof(RunTileIn) * run_resolve_slots(a.n_tiles)));
-  a.summaries = s->run_summaries.as<RunSummary>();
-  a.tile_in = s->run_tile_in.as<RunTileIn>();
-  a.counters = s->counters.as<unsigned long long>();
-  a.host_counters = s->host_counters;
-  a.out = s->out.as<uint64_t>();
-  a.out_cap = s->out_cap;
-  RJ_HIP(hipMemsetAsync(s->counters.p, 0, kCntSize * sizeof(unsigned long long), st));
-  s->host_counters[kCntFinal] = 0;
-  launch_pair_summary(a, s->t0(), nullptr, st);
-  launch_pair_resolve(a, st);
-  RJ_HIP(hipStreamSynchronize(st));   // (the number of pairs sizes the output)
-  RJ_HIP(hipGetLastError());
-  const uint64_t cnt = s->host_counters[kCntFinal];
-  if (!s->count_only_run) {
-    if (cnt > s->out_cap) {
-      const uint64_t cap = cnt + cnt / 16 + 1024;
-      RJ_HIP(s->out.reserve(cap * 2 * sizeof(uint64_t)));
-      s->out_cap = cap;
-    }
-    a.out = s->out.as<uint64_t>();
-    a.out_cap = s->out_cap;
-    if (cnt) launch_pair_emit(a, s->ev[2], st);
-    else RJ_HIP(hipEventRecord(s->ev[2], st));
-    RJ_HIP(hipStreamSynchronize(st));
-    RJ_HIP(hipGetLastError());
-    float ms = 0.f;
-    if (s->timing) (void)hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
-    s->stats.scan_ms += ms;
-  }
-  s->result_count = cnt;
-  s->result = s->count_only_run ? nullptr : s->out.as<uint64_t>();
-  s->hits_hint = cnt;
-  s->stats.n_hits += cnt;
-  s->stats.n_candidates += cnt;
-  s->stats.run_path = 2;
-  return 1;
+  RJ_TRY(run_params(s, d_text, n, 0, n, 0, &a));
+  return run_three_steps(s, a, true, s->count_only_run, st);
 }
 
 constexpr uint64_t kDenseSegment = 1ull << 27;  // dense mode: starts per pipeline run (bounds the lists)
 
-// One full pipeline over the starts [sb, se): scan -> region offsets -> verify -> finalize.
-// Results: s->out (device, ordered pairs), s->result_count.
-static int run_range(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, uint64_t carry_cur,
-                     uint64_t carry_prev_end, int have_prev, hipStream_t st, bool force_dense = false) {
-  const rj_program* rp = s->prog;
-  // Windows behind an unbounded prefix give ONE candidate per hit (the left-most start): enough for a
-  // run from the beginning of the text, not for an own range that begins inside it (a start clipped by
-  // the range or by a carried-in match would be missing) -- such runs, and repeats after a conflict,
-  // take the dense path, which considers every start.
-  const bool as_dense = force_dense || (rp->dev.behind && (sb != 0 || carry_cur != 0 || s->behind_conflicts));
+// One call of run_range: its arguments, and what is derived from them once.  (D may point at dense_copy: not to be copied.)
+struct RangeRun {
+  rj_scan* s;
+  const uint8_t* text;
+  uint64_t n, sb, se, carry_cur, carry_prev_end;
+  int have_prev;
+  hipStream_t st;
+  // effective_program
   DevProgram dense_copy;
+  const DevProgram* D;  // the program the kernels run: the pattern's own, or its dense copy
+  bool windows, behind;
+  uint32_t expand;  // candidate slots per hit (floating windows: one per possible start)
+  // plan_scan, once the routes in front of the scan kernels have passed
+  ChunkRange range;
+  ScanGeometry geo;
+  uint64_t region_full;  // a region that holds every position of its span
+  bool dense_walk, floating_regions, in_regions;
+  uint64_t region_cap;  // this attempt's
+
+  const rj_program* rp() const { return s->prog; }
+  bool fresh() const { return carry_cur == 0 && !have_prev; }
+  unsigned long long* counters() const { return s->counters.as<unsigned long long>(); }
+};
+
+// Windows behind an unbounded prefix give ONE candidate per hit (the left-most start): enough for a
+// run from the beginning of the text, not for an own range that begins inside it (a start clipped by
+// the range or by a carried-in match would be missing) -- such runs, and repeats after a conflict,
+// take the dense path, which considers every start.
+static void effective_program(RangeRun* r, bool force_dense) {
+  const rj_program* rp = r->rp();
+  const bool as_dense = force_dense || (rp->dev.behind && (r->sb != 0 || r->carry_cur != 0 || r->s->behind_conflicts));
+  r->D = &rp->dev;
   if (as_dense && rp->dev.mode == 1) {
-    dense_copy = rp->dev;
-    dense_copy.mode = 0;
-    dense_copy.behind = 0;
-    if (linear_path_cheap(rp)) dense_copy.max_walk = std::min<uint32_t>(dense_copy.max_walk, 4096u);
+    r->dense_copy = rp->dev;
+    r->dense_copy.mode = 0;
+    r->dense_copy.behind = 0;
+    if (linear_path_cheap(rp)) r->dense_copy.max_walk = std::min<uint32_t>(r->dense_copy.max_walk, 4096u);
+    r->D = &r->dense_copy;
   }
-  const DevProgram& D = (as_dense && rp->dev.mode == 1) ? dense_copy : rp->dev;
-  const bool windows = D.mode == 1;
-  const bool behind = windows && D.behind != 0;
-  s->result_count = 0;
-  s->result = nullptr;
-  // the previous text needed the linear-time path: go there directly (run_linear clears the hint
-  // when the text turns out not to need it)
-  // one long-lived thread in one loop position (run_scan.h): the text's bit streams answer, whatever the runs' length --
-  // after dense_streams (faster where the runs are short) has given such a text up, or at once for the patterns that
-  // kernel does not take (`a.*b`) and for runs under a carry
+  r->windows = r->D->mode == 1;
+  r->behind = r->windows && r->D->behind != 0;
+  r->expand = r->windows ? r->D->float_range : 1;
+}
+
+// The routes in front of the scan kernels, in the order they are tried.  1 = one of them answered, 0 = none did, < 0 = error.
+static int one_pass_routes(RangeRun& r) {
+  rj_scan* s = r.s;
+  const rj_program* rp = r.rp();
+  const uint8_t* d_text = r.text;
+  const uint64_t n = r.n, sb = r.sb, se = r.se, carry_cur = r.carry_cur, carry_prev_end = r.carry_prev_end;
+  const int have_prev = r.have_prev;
+  const bool windows = r.windows, fresh = r.fresh();
+  hipStream_t st = r.st;
   static const bool runs_first = getenv("RJ_RUNS_FIRST") != nullptr;   // measurement override
-  const bool fresh = carry_cur == 0 && !have_prev;
-  // (a pattern with a fast-forward window -- `a.*b`, `<[^>]*>`: the window is their first byte -- goes there only once a walk
-  // has outlived max_walk on this scan's text: linear_hint.  NOTE: the hint is cleared by nobody on this path; a scan object
-  // whose texts stop having long runs keeps the run kernels, which are never wrong and never quadratic.)
   static const bool no_pairs = getenv("RJ_NO_PAIRS") != nullptr;   // measurement override
   if (rp->run.pair && fresh && !no_pairs) {   // (`"[^"]*"`: every Q byte is a window hit and a walk; the pair kernels are two streaming passes)
-    int rc = run_pairs(s, d_text, n, sb, se, st);
-    if (rc != 0) return rc < 0 ? rc : RJ_OK;
+    if (int rc = run_pairs(s, d_text, n, sb, se, st)) return rc;
   }
   // A WINDOWS-mode run shape -- its window is the ONE byte of A: `a.*b`, `#.*`, `<[^>]*>`, `\([^)]*\)`, ` +` -- over a range that reaches the
   // text's end: the run kernels first.  On everyday text such a byte is everywhere, every hit is a walk, and the window path ran 1 GiB
@@ -727,268 +717,298 @@ static int run_range(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb,
   // (... and where the shape is `X+` / `X+ Y` -- ` +`, `=+`, `-+>` -- dense_streams decides runs of up to 47 bytes in registers in ONE pass:
   // ` +` over the same text 0.7 ms against the run kernels' 1.5; texts of longer runs send it back through streams_off, as in dense mode)
   if (window_runs && fresh && rp->stream.n_pos != 0 && rp->stream.run_shape != 0 && !rp->stream.select && !s->streams_off && !s->linear_hint && !runs_first) {
-    int rc = run_streams(s, d_text, n, sb, se, st);
-    if (rc != 0) return rc < 0 ? rc : RJ_OK;
+    if (int rc = run_streams(s, d_text, n, sb, se, st)) return rc;
   }
+  // One long-lived thread in one loop position (run_scan.h): the text's bit streams answer, whatever the runs' length -- after
+  // dense_streams (faster where the runs are short) has given such a text up, or at once for the patterns that kernel does not
+  // take and for runs under a carry.
+  // (a pattern with a fast-forward window -- `a.*b`, `<[^>]*>`: the window is their first byte -- goes there only once a walk
+  // has outlived max_walk on this scan's text: linear_hint.  NOTE: the hint is cleared by nobody on this path; a scan object
+  // whose texts stop having long runs keeps the run kernels, which are never wrong and never quadratic.)
   static const bool bol_dense_general = getenv("RJ_BOL_DENSE_GENERAL") != nullptr;   // measurement override: the policy before the in-kernel `^`
   const bool bol_dense = rp->run.bol != 0 && !windows && !runs_first && bol_dense_general;
   if (rp->run.ok && (runs_first || s->linear_hint || window_runs || (!windows && !bol_dense && (!fresh || rp->stream.n_pos == 0 || s->streams_off)))) {
-    int rc = run_runs(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st);
-    if (rc != 0) {
-      // (fewer than a match per 64 KiB: at ~11 ns per hit the window path wins below a hit per ~32 KiB)
-      if (rc == 1 && windows && !s->linear_hint) s->runs_sparse = s->result_count * 65536 < n - std::min(sb, n);
-      return rc < 0 ? rc : RJ_OK;
-    }
+    const int rc = run_runs(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st);
+    // (fewer than a match per 64 KiB: at ~11 ns per hit the window path wins below a hit per ~32 KiB)
+    if (rc == 1 && windows && !s->linear_hint) s->runs_sparse = s->result_count * 65536 < n - std::min(sb, n);
+    if (rc != 0) return rc;
   }
-  if (s->linear_hint && linear_path_fits(rp)) return run_linear(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st);
+  // the previous text needed the linear-time path: go there directly (run_linear clears the hint when the text turns out
+  // not to need it)
+  if (s->linear_hint && linear_path_fits(rp)) {
+    const int rc = run_linear(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st);
+    return rc != RJ_OK ? rc : 1;
+  }
   if (!windows && fresh) {
-    int rc = run_assertions(s, d_text, n, sb, se, st);
-    if (rc != 0) return rc < 0 ? rc : RJ_OK;
-    rc = run_streams(s, d_text, n, sb, se, st);
-    if (rc != 0) return rc < 0 ? rc : RJ_OK;
+    if (int rc = run_assertions(s, d_text, n, sb, se, st)) return rc;
+    if (int rc = run_streams(s, d_text, n, sb, se, st)) return rc;
     if (rp->run.ok && s->streams_off) {   // (dense_streams has just given this text up: long runs)
-      rc = run_runs(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st);
-      if (rc != 0) return rc < 0 ? rc : RJ_OK;
+      if (int rc = run_runs(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st)) return rc;
     }
   }
+  return 0;
+}
 
-  // what the scan kernel walks, in 1-KiB chunks
-  ScanParams sp{};
-  sp.text = d_text;
-  sp.n = n;
-  sp.sb = sb;
-  sp.se = se;
-  uint64_t first_chunk, end_chunk;
-  const uint32_t expand = windows ? D.float_range : 1;
-  if (windows) {
-    // fixed windows: w = s + offset.  floating: w in [s + float_min, s + float_max]
-    const uint64_t float_min = D.float_max + 1 - D.float_range;
-    sp.wlo = sb + (expand > 1 ? float_min : D.win_offset);
-    const uint64_t last_w = n >= D.win_len ? n - D.win_len + 1 : 0;  // a window must fit: w + len <= n
-    sp.whi = behind ? last_w : std::min(se + (expand > 1 ? D.float_max : D.win_offset), last_w);
-    if (sp.whi < sp.wlo) sp.whi = sp.wlo;
-    first_chunk = sp.wlo / 1024;
-    end_chunk = (sp.whi + 1023) / 1024;
-  } else {
-    first_chunk = sb / 1024;
-    end_chunk = (se + 1023) / 1024;
-  }
-  const uint64_t chunks = end_chunk > first_chunk ? end_chunk - first_chunk : 0;
-  const ScanGeometry geo = scan_geometry(std::max<uint64_t>(chunks, 1));
-  sp.span_chunks = geo.span_chunks;
+// What the scan kernel walks, in 1-KiB chunks, how its grid shares them, and which tail follows it.
+static void plan_scan(RangeRun* r) {
+  const DevProgram& D = *r->D;
+  // fixed windows: w = s + offset.  floating: w in [s + float_min, s + float_max]
+  const uint32_t float_min = D.float_max + 1 - D.float_range;
+  r->range = chunk_range(r->n, r->sb, r->se, r->windows, r->expand > 1 ? float_min : D.win_offset, r->expand > 1 ? D.float_max : D.win_offset,
+                         D.win_len, r->behind);
+  r->geo = scan_geometry(std::max<uint64_t>(r->range.chunks(), 1));
   // dense: any position may be a hit; windows: start small, grow on overflow
-  const uint64_t region_full = geo.span_chunks * 1024;
+  r->region_full = r->geo.span_chunks * 1024;
   // dense mode with a lane-sized automaton: one kernel finds, walks and compacts the candidates,
   // so its regions hold verified matches only (few) and are sized like the windows regions
   static const bool no_dense_walk = getenv("RJ_NO_DENSE_WALK") != nullptr;  // measurement override
-  const bool dense_walk = !windows && dense_walk_fits(D) && !no_dense_walk;
-  uint64_t region_cap = windows      ? std::min<uint64_t>(std::max<uint64_t>(s->region_cap_hint, 64), region_full)
-                        : dense_walk ? std::min<uint64_t>(std::max<uint64_t>(s->region_cap_hint, 256), region_full)
-                                     : region_full;
-
+  r->dense_walk = !r->windows && dense_walk_fits(D) && !no_dense_walk;
+  r->region_cap = r->windows      ? std::min<uint64_t>(std::max<uint64_t>(r->s->region_cap_hint, 64), r->region_full)
+                  : r->dense_walk ? std::min<uint64_t>(std::max<uint64_t>(r->s->region_cap_hint, 256), r->region_full)
+                                  : r->region_full;
   // fixed windows + an automaton that fits a lane: candidates are verified and compacted inside
   // their hit regions (no global compaction, no sort)
   static const bool no_float_regions = getenv("RJ_NO_FLOAT_REGIONS") != nullptr;  // measurement override
-  const bool floating_regions = windows && expand > 1 && D.n_words <= 4 && !no_float_regions;
-  const bool in_regions = (windows && D.n_words <= 4 && (expand == 1 || floating_regions)) || dense_walk;  // (behind: n_words <= 4 by plan)
+  r->floating_regions = r->windows && r->expand > 1 && D.n_words <= 4 && !no_float_regions;
+  r->in_regions = (r->windows && D.n_words <= 4 && (r->expand == 1 || r->floating_regions)) || r->dense_walk;  // (behind: n_words <= 4 by plan)
+}
 
+static ScanParams scan_params(const RangeRun& r) {
+  ScanParams sp{};
+  sp.text = r.text;
+  sp.n = r.n;
+  sp.sb = r.sb;
+  sp.se = r.se;
+  sp.wlo = r.range.wlo;
+  sp.whi = r.range.whi;
+  sp.span_chunks = r.geo.span_chunks;
+  sp.hits = r.s->hits.as<uint64_t>();
+  sp.region_cap = static_cast<uint32_t>(r.region_cap);
+  sp.hit_counts = r.s->hit_counts.as<uint32_t>();
+  if (r.in_regions && r.windows) sp.zero_counters = r.counters();  // the scan kernel clears them
+  return sp;
+}
+
+static VerifyParams verify_params(const RangeRun& r) {
+  VerifyParams vp{};
+  vp.text = r.text;
+  vp.n = r.n;
+  vp.hits = r.s->hits.as<uint64_t>();
+  vp.offsets = r.s->hit_offsets.as<uint64_t>();
+  vp.n_regions = r.geo.n_regions;
+  vp.region_cap = static_cast<uint32_t>(r.region_cap);
+  vp.cand_begin = r.s->cand_begin.as<uint64_t>();
+  vp.cand_end = r.s->cand_end.as<uint64_t>();
+  vp.counters = r.counters();
+  vp.sb = r.sb;
+  vp.se = r.se;
+  vp.expand = r.expand;
+  vp.float_max = r.D->float_max;
+  return vp;
+}
+
+static FinalizeParams finalize_params(const RangeRun& r) {
+  FinalizeParams fp{};
+  fp.cand_begin = r.s->cand_begin.as<uint64_t>();
+  fp.cand_end = r.s->cand_end.as<uint64_t>();
+  fp.cands_cap = r.s->cands_cap;
+  fp.out = r.s->out.as<uint64_t>();
+  fp.out_cap = r.s->out_cap;
+  fp.counters = r.counters();
+  fp.carry_cur = r.carry_cur;
+  fp.carry_prev_end = r.carry_prev_end;
+  fp.have_prev = r.have_prev;
+  // bit-exactness with the reference's ring artefact (Q8) can only be at stake when the
+  // pattern is at risk AND a candidate begins exactly where another one ends
+  // (from the text's beginning: the range [0, se) of a pattern too wide for the exact replay included -- run_pipeline)
+  fp.detect_adjacent = r.rp()->host->q8_risk && r.sb == 0 && r.fresh();
+  fp.detect_conflict = r.behind;
+  fp.expand = r.expand;
+  return fp;
+}
+
+// This attempt's lists and counters, and the scan kernel over them.
+static int enqueue_scan(const RangeRun& r) {
+  rj_scan* s = r.s;
+  const DevProgram& D = *r.D;
+  const uint64_t slots = static_cast<uint64_t>(r.geo.n_regions) * r.region_cap;
+  // candidate slots: one per (hit, possible start); floating windows start with room for a few
+  // thousand hits and grow when a run needs more
+  const uint64_t cand_slots = (r.expand == 1 || r.floating_regions) ? slots : std::max<uint64_t>(s->hits_hint * r.expand * 2, 1u << 16);
+  RJ_TRY(ensure_lists(s, r.geo.n_regions, static_cast<uint32_t>(r.region_cap), std::max<uint64_t>(cand_slots, 1u << 12)));
+  if (r.in_regions) RJ_HIP(s->valid_counts.reserve(static_cast<size_t>(r.geo.n_regions) * sizeof(uint32_t)));
+  const ScanParams sp = scan_params(r);
+  if (sp.zero_counters == nullptr) RJ_HIP(hipMemsetAsync(s->counters.p, 0, kCntSize * sizeof(unsigned long long), r.st));
+  if (r.windows) {
+    const WindowSet ws = make_window_set(r.rp());
+    launch_scan_windows(sp, ws, D.n_windows, r.geo.grid, s->t0(), s->ev[2], r.st);
+  } else if (r.dense_walk) {
+    launch_scan_dense_walk(sp, D, r.geo.grid, s->cand_end.as<uint64_t>(), r.counters(), s->t0(), s->ev[2], r.st);
+  } else {
+    launch_scan_dense(sp, D, r.geo.grid, s->t0(), s->ev[2], r.st);
+  }
+  return RJ_OK;
+}
+
+// ---- the in-region tail: verify + compact inside the regions, lay the survivors out, check / select: one sync
+// (verifying at the tail of the scan kernel instead was measured: 5 us slower per pass)
+// What the lay-out reads: per region the number of survivors, their begins and (cand_end) ends; its scratch when it takes two launches.
+struct RegionLists {
+  const uint32_t* survivors;
+  const uint64_t* begins;
+  uint64_t *off_scratch, *prev_scratch;
+};
+
+// Verify in the form the plan asks for, each with the launcher that takes what its LDS walker does not.  *local_select:
+// floating windows: the wave that verifies a region also applies the selection rule to the region's candidates, which then
+// usually are the result already (verify_lds.hip) -- cleared when the fallback, which has no such rule, ran.
+static RegionLists verify_regions(const RangeRun& r, const VerifyParams& vp, bool* local_select) {
+  rj_scan* s = r.s;
+  const DevProgram& D = *r.D;
+  uint32_t *hit_counts = s->hit_counts.as<uint32_t>(), *valid_counts = s->valid_counts.as<uint32_t>();
+  uint64_t *cand_begin = s->cand_begin.as<uint64_t>(), *cand_end = s->cand_end.as<uint64_t>();
+  RegionLists l{r.dense_walk ? hit_counts : valid_counts, s->hits.as<uint64_t>(), nullptr, nullptr};  // (scan_dense_walk has verified and compacted)
+  if (r.floating_regions) {
+    if (!launch_verify_floating_lds(vp, D, r.rp()->walk, hit_counts, valid_counts, cand_begin, cand_end, *local_select, r.st)) {
+      *local_select = false;
+      launch_verify_floating_in_regions(vp, D, hit_counts, valid_counts, cand_begin, cand_end, r.st);
+    }
+    l.begins = cand_begin;
+  } else if (r.behind) {
+    if (!launch_verify_behind_lds(vp, D, r.rp()->walk, hit_counts, valid_counts, cand_end, r.st))
+      launch_verify_behind_in_regions(vp, D, r.rp()->rev, hit_counts, valid_counts, cand_end, r.st);
+  } else if (!r.dense_walk) {
+    launch_verify_in_regions(vp, D, hit_counts, valid_counts, cand_end, r.st);
+  }
+  return l;
+}
+
+// offsets + gather + check in one kernel (two with scratch), which writes the counters into pinned host memory; synchronised.
+static int layout_and_check(const RangeRun& r, const FinalizeParams& fp, const RegionLists& l) {
+  rj_scan* s = r.s;
+  launch_offsets_gather_check(l.survivors, l.begins, s->cand_end.as<uint64_t>(), r.geo.n_regions, static_cast<uint32_t>(r.region_cap),
+                              fp.carry_cur, s->out.as<uint64_t>(), s->out_cap, r.counters(), s->host_counters, l.off_scratch,
+                              l.prev_scratch, r.st, fp.carry_prev_end, fp.have_prev);
+  return synchronise(r.st);
+}
+
+static int region_tail(const RangeRun& r, const FinalizeParams& fp) {
+  rj_scan* s = r.s;
+  hipStream_t st = r.st;
+  const VerifyParams vp = verify_params(r);
+  // (not for patterns at risk of the ring artefact: the adjacency test below wants every candidate)
+  bool local_select = r.floating_regions && !r.rp()->host->q8_risk && !s->no_local_select && getenv("RJ_NO_LOCAL_SELECT") == nullptr;
+  RegionLists l = verify_regions(r, vp, &local_select);
+  // (letting the last workgroup publish the counters to pinned host memory instead of the copy
+  // below was measured: slower, its agent-scope fence writes L2 back)
+  s->host_counters[kCntUnordered] = 0;  // the kernel below writes the pinned block itself
+  s->host_counters[kCntAdjacent] = 0;
+  s->host_counters[kCntConflict] = 0;
+  // many candidates per region expected (the previous run had them, or the pattern is dense: its FIRST run
+  // over a text has no history, and the one-launch form took 20 ms for the 8.4 M matches of `x*` over 16 MiB
+  // where the second launch costs microseconds when there is little to copy): lay out first, then copy with a
+  // wave per region
+  if (r.dense_walk || s->hits_hint > static_cast<uint64_t>(r.geo.n_regions) * 16) {
+    RJ_HIP(s->hit_offsets.reserve((static_cast<size_t>(r.geo.n_regions) + 1) * sizeof(uint64_t)));
+    RJ_HIP(s->scan_a.reserve(static_cast<size_t>(r.geo.n_regions) * sizeof(uint64_t)));
+    l.off_scratch = s->hit_offsets.as<uint64_t>();
+    l.prev_scratch = s->scan_a.as<uint64_t>();
+  }
+  RJ_TRY(layout_and_check(r, fp, l));
+  if (local_select && s->host_counters[kCntUnordered] != 0 && s->host_counters[kCntOverflow] == 0 && s->host_counters[kCntOverrun] == 0) {
+    // a match reaches from one region into the candidates of the next: the general selection needs every
+    // candidate -- verify once more without the in-region rule (the hit lists are untouched: floating
+    // candidates go to their own arrays), and remember it for this scan's next runs
+    s->no_local_select = true;
+    s->stats.retries++;
+    launch_verify_floating_lds(vp, *r.D, r.rp()->walk, s->hit_counts.as<uint32_t>(), s->valid_counts.as<uint32_t>(),
+                               s->cand_begin.as<uint64_t>(), s->cand_end.as<uint64_t>(), false, st);
+    s->host_counters[kCntUnordered] = 0;
+    RJ_TRY(layout_and_check(r, fp, l));
+  }
+  if (s->host_counters[kCntUnordered] != 0 && s->host_counters[kCntOverflow] == 0) {
+    // not the result yet: the selection kernels work on begin[] / end[]
+    const uint64_t nc = s->host_counters[kCntCands];
+    RJ_HIP(s->keys_out.reserve(nc * sizeof(uint64_t)));
+    RJ_HIP(s->vals_out.reserve(nc * sizeof(uint64_t)));
+    launch_split_pairs(s->out.as<uint64_t>(), r.counters() + kCntCands, nc, s->keys_out.as<uint64_t>(), s->vals_out.as<uint64_t>(), st);
+    // behind: one candidate per hit, in hit order -- their begins are not sorted (a later hit may have an earlier left-most
+    // start).  Few candidates are sorted by finalize_small; many here (the region ends are consumed by the gather already).
+    if (r.behind && nc > kFinalizeCap) RJ_TRY(sort_by_begin(s, nc, r.n + 1, st));
+    if (fp.detect_adjacent) {
+      // (overlapping candidates: adjacency is no longer a neighbour property)
+      launch_detect_adjacent(s->keys_out.as<uint64_t>(), s->vals_out.as<uint64_t>(), nc, r.counters(), st);
+      RJ_HIP(hipMemcpyAsync(&s->host_counters[kCntAdjacent], r.counters() + kCntAdjacent, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      RJ_HIP(hipStreamSynchronize(st));
+    }
+  }
+  return resolve_selection(s, fp, st);
+}
+
+// ---- the list tail (automata of more than 128 positions, floating windows outside the regions): region_offsets -> verify_wave
+// -> finalize_small, which answers or leaves kCntFinal = ~0 for finalize_large.  (fp is filled BEFORE the lists may grow below:
+// a run whose candidates outgrew them has more than finalize_small takes, and finalize_large reads the scan's own buffers.)
+static int list_tail(const RangeRun& r, const FinalizeParams& fp) {
+  rj_scan* s = r.s;
+  hipStream_t st = r.st;
+  launch_region_offsets(s->hit_counts.as<uint32_t>(), r.geo.n_regions, static_cast<uint32_t>(r.region_cap), s->hit_offsets.as<uint64_t>(),
+                        r.counters(), st);
+  VerifyParams vp = verify_params(r);
+  if (r.expand > 1 && !r.floating_regions) {
+    // the slot count depends on the hit count, which only the device knows yet: verify must not
+    // write past the candidate arrays, so floating runs read the count first (hits are rare)
+    RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    RJ_HIP(hipStreamSynchronize(st));
+    if (s->host_counters[kCntOverflow] == 0) {
+      const uint64_t need = s->host_counters[kCntHits] * r.expand;
+      RJ_TRY(ensure_lists(s, r.geo.n_regions, static_cast<uint32_t>(r.region_cap), std::max<uint64_t>(need, s->cands_cap)));
+      vp.cand_begin = s->cand_begin.as<uint64_t>();
+      vp.cand_end = s->cand_end.as<uint64_t>();
+    }
+  }
+  launch_verify(vp, *r.D, r.windows ? std::max<uint64_t>(s->hits_hint, 1u << 14) : (r.se - r.sb) / 8 + 1, st);
+  launch_finalize_small(fp, st);
+  return read_counters(s, st);
+}
+
+// One full pipeline over the starts [sb, se): the one-pass routes, else scan -> tail (in the regions, or the lists) until the
+// regions held their hits.  Results: s->out (device, ordered pairs), s->result_count.
+static int run_range(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, uint64_t carry_cur,
+                     uint64_t carry_prev_end, int have_prev, hipStream_t st, bool force_dense = false) {
+  const rj_program* rp = s->prog;
+  RangeRun r{s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st};
+  effective_program(&r, force_dense);
+  s->result_count = 0;
+  s->result = nullptr;
+  if (int rc = one_pass_routes(r)) return rc < 0 ? rc : RJ_OK;
+  plan_scan(&r);
   for (int attempt = 0; attempt < 6; attempt++) {
-    const uint64_t slots = static_cast<uint64_t>(geo.n_regions) * region_cap;
-    // candidate slots: one per (hit, possible start); floating windows start with room for a few
-    // thousand hits and grow when a run needs more
-    uint64_t cand_slots = (expand == 1 || floating_regions) ? slots : std::max<uint64_t>(s->hits_hint * expand * 2, 1u << 16);
-    int rc = ensure_lists(s, geo.n_regions, static_cast<uint32_t>(region_cap), std::max<uint64_t>(cand_slots, 1u << 12));
-    if (rc != RJ_OK) return rc;
-    if (in_regions) RJ_HIP(s->valid_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
-    sp.hits = s->hits.as<uint64_t>();
-    sp.region_cap = static_cast<uint32_t>(region_cap);
-    sp.hit_counts = s->hit_counts.as<uint32_t>();
-    if (in_regions && windows) sp.zero_counters = s->counters.as<unsigned long long>();  // the scan kernel clears them
-    else RJ_HIP(hipMemsetAsync(s->counters.p, 0, kCntSize * sizeof(unsigned long long), st));
-    if (windows) {
-      const WindowSet ws = make_window_set(rp);
-      launch_scan_windows(sp, ws, D.n_windows, geo.grid, s->t0(), s->ev[2], st);
-    } else if (dense_walk) {
-      launch_scan_dense_walk(sp, D, geo.grid, s->cand_end.as<uint64_t>(), s->counters.as<unsigned long long>(), s->t0(),
-                             s->ev[2], st);
-    } else {
-      launch_scan_dense(sp, D, geo.grid, s->t0(), s->ev[2], st);
-    }
-    FinalizeParams fp{};
-    fp.cand_begin = s->cand_begin.as<uint64_t>();
-    fp.cand_end = s->cand_end.as<uint64_t>();
-    fp.cands_cap = s->cands_cap;
-    fp.out = s->out.as<uint64_t>();
-    fp.out_cap = s->out_cap;
-    fp.counters = s->counters.as<unsigned long long>();
-    fp.carry_cur = carry_cur;
-    fp.carry_prev_end = carry_prev_end;
-    fp.have_prev = have_prev;
-    // bit-exactness with the reference's ring artefact (Q8) can only be at stake when the
-    // pattern is at risk AND a candidate begins exactly where another one ends
-    // (from the text's beginning: the range [0, se) of a pattern too wide for the exact replay included -- run_pipeline)
-    const bool from_start = sb == 0 && carry_cur == 0 && !have_prev;
-    fp.detect_adjacent = rp->host->q8_risk && from_start;
-    fp.detect_conflict = behind;
-    fp.expand = expand;
-    VerifyParams vp{};
-    if (!in_regions)
-      launch_region_offsets(s->hit_counts.as<uint32_t>(), geo.n_regions, static_cast<uint32_t>(region_cap),
-                            s->hit_offsets.as<uint64_t>(), s->counters.as<unsigned long long>(), st);
-    vp.text = d_text;
-    vp.n = n;
-    vp.hits = s->hits.as<uint64_t>();
-    vp.offsets = s->hit_offsets.as<uint64_t>();
-    vp.n_regions = geo.n_regions;
-    vp.region_cap = static_cast<uint32_t>(region_cap);
-    vp.cand_begin = s->cand_begin.as<uint64_t>();
-    vp.cand_end = s->cand_end.as<uint64_t>();
-    vp.counters = s->counters.as<unsigned long long>();
-    vp.sb = sb;
-    vp.se = se;
-    vp.expand = expand;
-    vp.float_max = D.float_max;
-    if (expand > 1 && !floating_regions) {
-      // the slot count depends on the hit count, which only the device knows yet: verify must not
-      // write past the candidate arrays, so floating runs read the count first (hits are rare)
-      RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      RJ_HIP(hipStreamSynchronize(st));
-      if (s->host_counters[kCntOverflow] == 0) {
-        const uint64_t need = s->host_counters[kCntHits] * expand;
-        rc = ensure_lists(s, geo.n_regions, static_cast<uint32_t>(region_cap), std::max<uint64_t>(need, s->cands_cap));
-        if (rc != RJ_OK) return rc;
-        vp.cand_begin = s->cand_begin.as<uint64_t>();
-        vp.cand_end = s->cand_end.as<uint64_t>();
-      }
-    }
-    if (in_regions) {
-      // verify + compact inside the regions, lay the survivors out, check / select: one sync
-      // (verifying at the tail of the scan kernel instead was measured: 5 us slower per pass)
-      const uint64_t* begins = s->hits.as<uint64_t>();
-      // floating windows: the wave that verifies a region also applies the selection rule to the region's candidates,
-      // which then usually are the result already (verify_lds.hip); not for patterns at risk of the ring artefact
-      // (the adjacency test below wants every candidate)
-      bool local_select = floating_regions && !rp->host->q8_risk && !s->no_local_select && getenv("RJ_NO_LOCAL_SELECT") == nullptr;
-      if (floating_regions) {
-        if (!launch_verify_floating_lds(vp, D, rp->walk, s->hit_counts.as<uint32_t>(), s->valid_counts.as<uint32_t>(),
-                                        s->cand_begin.as<uint64_t>(), s->cand_end.as<uint64_t>(), local_select, st)) {
-          local_select = false;
-          launch_verify_floating_in_regions(vp, D, s->hit_counts.as<uint32_t>(), s->valid_counts.as<uint32_t>(),
-                                            s->cand_begin.as<uint64_t>(), s->cand_end.as<uint64_t>(), st);
-        }
-        begins = s->cand_begin.as<uint64_t>();
-      } else if (behind) {
-        if (!launch_verify_behind_lds(vp, D, rp->walk, s->hit_counts.as<uint32_t>(), s->valid_counts.as<uint32_t>(),
-                                      s->cand_end.as<uint64_t>(), st))
-          launch_verify_behind_in_regions(vp, D, rp->rev, s->hit_counts.as<uint32_t>(), s->valid_counts.as<uint32_t>(),
-                                          s->cand_end.as<uint64_t>(), st);
-      } else if (!dense_walk) {
-        launch_verify_in_regions(vp, D, s->hit_counts.as<uint32_t>(), s->valid_counts.as<uint32_t>(), s->cand_end.as<uint64_t>(), st);
-      }
-      const uint32_t* survivors = dense_walk ? s->hit_counts.as<uint32_t>() : s->valid_counts.as<uint32_t>();
-      // (letting the last workgroup publish the counters to pinned host memory instead of the copy
-      // below was measured: slower, its agent-scope fence writes L2 back)
-      s->host_counters[kCntUnordered] = 0;  // the kernel below writes the pinned block itself
-      s->host_counters[kCntAdjacent] = 0;
-      s->host_counters[kCntConflict] = 0;
-      // many candidates per region expected (the previous run had them, or the pattern is dense: its FIRST run
-      // over a text has no history, and the one-launch form took 20 ms for the 8.4 M matches of `x*` over 16 MiB
-      // where the second launch costs microseconds when there is little to copy): lay out first, then copy with a
-      // wave per region
-      uint64_t *off_scratch = nullptr, *prev_scratch = nullptr;
-      if (dense_walk || s->hits_hint > static_cast<uint64_t>(geo.n_regions) * 16) {
-        RJ_HIP(s->hit_offsets.reserve((static_cast<size_t>(geo.n_regions) + 1) * sizeof(uint64_t)));
-        RJ_HIP(s->scan_a.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint64_t)));
-        off_scratch = s->hit_offsets.as<uint64_t>();
-        prev_scratch = s->scan_a.as<uint64_t>();
-      }
-      launch_offsets_gather_check(survivors, begins, s->cand_end.as<uint64_t>(), geo.n_regions,
-                                  static_cast<uint32_t>(region_cap), fp.carry_cur, s->out.as<uint64_t>(), s->out_cap,
-                                  s->counters.as<unsigned long long>(), s->host_counters, off_scratch, prev_scratch, st,
-                                  fp.carry_prev_end, fp.have_prev);
-      RJ_HIP(hipStreamSynchronize(st));
-      RJ_HIP(hipGetLastError());
-      if (local_select && s->host_counters[kCntUnordered] != 0 && s->host_counters[kCntOverflow] == 0 && s->host_counters[kCntOverrun] == 0) {
-        // a match reaches from one region into the candidates of the next: the general selection needs every
-        // candidate -- verify once more without the in-region rule (the hit lists are untouched: floating
-        // candidates go to their own arrays), and remember it for this scan's next runs
-        s->no_local_select = true;
-        s->stats.retries++;
-        launch_verify_floating_lds(vp, D, rp->walk, s->hit_counts.as<uint32_t>(), s->valid_counts.as<uint32_t>(),
-                                   s->cand_begin.as<uint64_t>(), s->cand_end.as<uint64_t>(), false, st);
-        s->host_counters[kCntUnordered] = 0;
-        launch_offsets_gather_check(survivors, begins, s->cand_end.as<uint64_t>(), geo.n_regions,
-                                    static_cast<uint32_t>(region_cap), fp.carry_cur, s->out.as<uint64_t>(), s->out_cap,
-                                    s->counters.as<unsigned long long>(), s->host_counters, off_scratch, prev_scratch, st,
-                                    fp.carry_prev_end, fp.have_prev);
-        RJ_HIP(hipStreamSynchronize(st));
-        RJ_HIP(hipGetLastError());
-      }
-      if (s->host_counters[kCntUnordered] != 0 && s->host_counters[kCntOverflow] == 0) {
-        // not the result yet: the selection kernels work on begin[] / end[]
-        const uint64_t nc = s->host_counters[kCntCands];
-        RJ_HIP(s->keys_out.reserve(nc * sizeof(uint64_t)));
-        RJ_HIP(s->vals_out.reserve(nc * sizeof(uint64_t)));
-        launch_split_pairs(s->out.as<uint64_t>(), s->counters.as<unsigned long long>() + kCntCands, nc,
-                           s->keys_out.as<uint64_t>(), s->vals_out.as<uint64_t>(), st);
-        if (behind && nc > kFinalizeCap) {
-          // one candidate per hit, in hit order: their begins are not sorted (a later hit may have an
-          // earlier left-most start).  Few candidates are sorted by finalize_small; many here.
-          unsigned bits = 1;
-          while (bits < 64 && ((n + 1) >> bits) != 0) bits++;
-          RJ_HIP(s->cand_begin.reserve(nc * sizeof(uint64_t)));
-          uint64_t* k2 = s->cand_begin.as<uint64_t>();
-          uint64_t* v2 = s->cand_end.as<uint64_t>();   // (region ends: consumed by the gather already)
-          RJ_HIP(s->cand_end.reserve(nc * sizeof(uint64_t)));
-          v2 = s->cand_end.as<uint64_t>();
-          size_t tmp_bytes = 0;
-          RJ_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, s->keys_out.as<uint64_t>(), k2, s->vals_out.as<uint64_t>(), v2, nc, 0, bits, st));
-          RJ_HIP(s->sort_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
-          RJ_HIP(rocprim::radix_sort_pairs(s->sort_tmp.p, tmp_bytes, s->keys_out.as<uint64_t>(), k2, s->vals_out.as<uint64_t>(), v2, nc, 0, bits, st));
-          RJ_HIP(hipMemcpyAsync(s->keys_out.p, k2, nc * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-          RJ_HIP(hipMemcpyAsync(s->vals_out.p, v2, nc * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-        }
-        if (fp.detect_adjacent) {
-          // (overlapping candidates: adjacency is no longer a neighbour property)
-          launch_detect_adjacent(s->keys_out.as<uint64_t>(), s->vals_out.as<uint64_t>(), nc, s->counters.as<unsigned long long>(), st);
-          RJ_HIP(hipMemcpyAsync(&s->host_counters[kCntAdjacent], s->counters.as<unsigned long long>() + kCntAdjacent,
-                                sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-          RJ_HIP(hipStreamSynchronize(st));
-        }
-      }
-      rc = resolve_selection(s, fp, st);
-      if (rc != RJ_OK) return rc;
-      if (behind && s->host_counters[kCntOverflow] == 0 && (s->host_counters[kCntConflict] != 0 || s->host_counters[kCntOverrun] != 0)) {
-        // a hidden candidate reaches beyond the match that hides it, or a walk from a hit ran into the
-        // limit: every start has to be considered -- the dense path (and behind it the carry scan)
-        s->behind_conflicts = true;
-        s->stats.retries++;
-        return run_range(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st, true);
-      }
-    } else {
-      launch_verify(vp, D, windows ? std::max<uint64_t>(s->hits_hint, 1u << 14) : (se - sb) / 8 + 1, st);
-      launch_finalize_small(fp, st);
-      RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      RJ_HIP(hipStreamSynchronize(st));
-      RJ_HIP(hipGetLastError());
+    RJ_TRY(enqueue_scan(r));
+    const FinalizeParams fp = finalize_params(r);
+    RJ_TRY(r.in_regions ? region_tail(r, fp) : list_tail(r, fp));
+    if (r.in_regions && r.behind && s->host_counters[kCntOverflow] == 0 &&
+        (s->host_counters[kCntConflict] != 0 || s->host_counters[kCntOverrun] != 0)) {
+      // a hidden candidate reaches beyond the match that hides it, or a walk from a hit ran into the
+      // limit: every start has to be considered -- the dense path (and behind it the carry scan)
+      s->behind_conflicts = true;
+      s->stats.retries++;
+      return run_range(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st, true);
     }
     const unsigned long long n_hits = s->host_counters[kCntHits];
-    float ms = 0.f;
-    if (s->timing) (void)hipEventElapsedTime(&ms, s->ev[1], s->ev[2]);
-    s->stats.scan_ms += ms;
+    add_scan_ms(s);
     s->stats.n_hits += n_hits;
     if (s->host_counters[kCntOverflow] != 0 && s->host_counters[kCntOverrun] == 0) {
       // a region overflowed: size every region for the fullest one seen (x2) and run again
       s->stats.retries++;
-      const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(s->host_counters[kCntMaxRegion] * 2, region_cap * 4), region_full);
-      if (want <= region_cap) return fail(RJ_DEVICE_ERROR, "hit regions cannot grow further");
-      region_cap = want;
+      const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(s->host_counters[kCntMaxRegion] * 2, r.region_cap * 4), r.region_full);
+      if (want <= r.region_cap) return fail(RJ_DEVICE_ERROR, "hit regions cannot grow further");
+      r.region_cap = want;
       s->region_cap_hint = static_cast<uint32_t>(std::min<uint64_t>(want, 1u << 20));
       s->stats.n_hits -= n_hits;
       continue;
     }
     s->hits_hint = n_hits;
-    if (windows && rp->run.ok && n_hits * 32768 > se - sb) s->window_dense = true;   // (a hit every 32 KiB or denser: the run kernels from now on)
+    if (r.windows && rp->run.ok && n_hits * 32768 > se - sb) s->window_dense = true;   // (a hit every 32 KiB or denser: the run kernels from now on)
     if (s->host_counters[kCntOverrun] != 0) {
       // some start was still alive after max_walk bytes (an unbounded repetition over a long run):
       // walking every start on its own is quadratic there.  The carry scan is linear in the text
@@ -996,16 +1016,14 @@ static int run_range(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb,
       s->linear_hint = true;
       s->stats.retries++;
       if (rp->run.ok) {   // one long-lived thread in one loop position: the run kernels (two passes over the text)
-        rc = run_runs(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st);
-        if (rc != 0) return rc < 0 ? rc : RJ_OK;
+        if (int rc = run_runs(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st)) return rc < 0 ? rc : RJ_OK;
       }
       return run_linear(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st);
     }
-    if (in_regions) {
-      // check_and_select produced the result
+    if (r.in_regions) {
+      // resolve_selection produced the result
     } else if (s->host_counters[kCntFinal] == ~0ull) {
-      rc = finalize_large(s, n_hits * expand, expand > 1, n + 1, fp, st);
-      if (rc != RJ_OK) return rc;
+      RJ_TRY(finalize_large(s, n_hits * r.expand, r.expand > 1, n + 1, fp, st));
     } else {
       s->result_count = s->host_counters[kCntFinal];
       s->stats.n_candidates += s->host_counters[kCntCands];
@@ -1022,13 +1040,10 @@ static int run_range(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb,
 static int run_exact_one_lane(rj_scan* s, const uint8_t* d_text, uint64_t n, hipStream_t st) {
   const rj_program* rp = s->prog;
   RJ_HIP(s->ring.reserve(static_cast<size_t>(rp->graph.times) * rp->graph.n_states * sizeof(int64_t)));
-  int rc = ensure_lists(s, 1, 1, std::max<uint64_t>(s->cands_cap, n + 2));
-  if (rc != RJ_OK) return rc;
+  RJ_TRY(ensure_lists(s, 1, 1, std::max<uint64_t>(s->cands_cap, n + 2)));
   launch_exact_sequential(d_text, n, rp->graph, s->ring.as<int64_t>(), s->out.as<uint64_t>(), s->out_cap,
                           s->counters.as<unsigned long long>(), st);
-  RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  RJ_HIP(hipStreamSynchronize(st));
-  RJ_HIP(hipGetLastError());
+  RJ_TRY(read_counters(s, st));
   s->result_count = s->host_counters[kCntFinal];
   s->result = s->out.as<uint64_t>();
   return RJ_OK;
@@ -1060,12 +1075,17 @@ static int keep_begins(rj_scan* s, uint64_t lo, uint64_t hi, hipStream_t st) {
     return RJ_OK;
   };
   uint64_t i = 0, j = 0;
-  int rc = first_at_or_after(lo, &i);
-  if (rc != RJ_OK) return rc;
-  rc = first_at_or_after(hi, &j);
-  if (rc != RJ_OK) return rc;
+  RJ_TRY(first_at_or_after(lo, &i));
+  RJ_TRY(first_at_or_after(hi, &j));
   s->result += 2 * i;
   s->result_count = j - i;
+  return RJ_OK;
+}
+
+// a finished call's stats: the host clock since wall0, the number of matches
+static int finish_stats(rj_scan* s, std::chrono::steady_clock::time_point wall0) {
+  s->stats.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  s->stats.n_matches = s->result_count;
   return RJ_OK;
 }
 
@@ -1093,9 +1113,7 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
     if (rc < 0) return rc;
     if (rc == 1) {
       s->stats.exact_path = s->xr_parts != 0 ? 2 : 1;
-      s->stats.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-      s->stats.n_matches = s->result_count;
-      return RJ_OK;
+      return finish_stats(s, wall0);
     }
     // (a stretch the replay cannot take: the range still owns the segments between the same points, answered below)
     if (!s->xr_ends_known) return refuse_exact(s);
@@ -1141,19 +1159,13 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
     // move -- it is launch + kernel, not the wake-up -- and results occasionally arrived stale.)
     s->small_hdr[1] = 1;
     launch_match_small(sp, rp->dev, st);
-    RJ_HIP(hipStreamSynchronize(st));
-    RJ_HIP(hipGetLastError());
+    RJ_TRY(synchronise(st));
     if (s->small_hdr[1] == 0) {
       s->result_count = s->small_hdr[0];
       s->result = s->small_out;   // pinned host memory: readable from the device and from the host
-      if (cut_range) {
-        int rc = keep_begins(s, keep_from, se, st);
-        if (rc != RJ_OK) return rc;
-      }
+      if (cut_range) RJ_TRY(keep_begins(s, keep_from, se, st));
       s->stats.n_candidates = s->result_count;
-      s->stats.n_matches = s->result_count;
-      s->stats.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-      return RJ_OK;
+      return finish_stats(s, wall0);
     }
     // too many candidates, a long walk, or a Q8-sensitive adjacency: the general pipeline
   }
@@ -1162,8 +1174,7 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
   const bool single_run = windows || dense_walk_fits(rp->dev) || se - sb <= kDenseSegment || (s->linear_hint && linear_path_fits(rp)) ||
                           (rp->run.pair != 0 && whole_text);
   if (single_run) {
-    int rc = run_range(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st);
-    if (rc != RJ_OK) return rc;
+    RJ_TRY(run_range(s, d_text, n, sb, se, carry_cur, carry_prev_end, have_prev, st));
     // (the carry scan may have accumulated segments elsewhere; a count-only run of the run kernels leaves no list)
     if (s->result == nullptr && !(s->count_only_run && s->stats.run_path)) s->result = s->out.as<uint64_t>();
   } else {
@@ -1175,8 +1186,7 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
       // (once a segment needed the carry scan the rest of the range goes there in one piece: its
       // summaries cover the text to its end, so many small runs would repeat that work)
       hi = (s->linear_hint && linear_path_fits(rp)) ? se : std::min(se, lo + kDenseSegment);
-      int rc = run_range(s, d_text, n, lo, hi, carry_cur, carry_prev_end, have_prev, st);
-      if (rc != RJ_OK) return rc;
+      RJ_TRY(run_range(s, d_text, n, lo, hi, carry_cur, carry_prev_end, have_prev, st));
       if (s->result_count) {
         const uint64_t* from = s->result ? s->result : s->out.as<uint64_t>();
         RJ_HIP(s->acc_out.grow_keep((total + s->result_count) * 2 * sizeof(uint64_t), total * 2 * sizeof(uint64_t)));
@@ -1210,15 +1220,10 @@ int run_pipeline(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uin
     if (rc == 0) return refuse_exact(s);
     s->stats.exact_path = s->xr_parts != 0 ? 2 : 1;
   }
-  if (cut_range) {
-    int rc = keep_begins(s, keep_from, se, st);
-    if (rc != RJ_OK) return rc;
-  }
+  if (cut_range) RJ_TRY(keep_begins(s, keep_from, se, st));
   // (every run_range ends with a stream synchronise, so the host clock covers the whole pipeline
   // and no event commands are needed on the stream)
-  s->stats.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-  s->stats.n_matches = s->result_count;
-  return RJ_OK;
+  return finish_stats(s, wall0);
 }
 
 static int scan_init(rj_scan* s) {
@@ -1259,8 +1264,7 @@ int rj_compile(const char* regexp, rj_program** out) {
   rp->pattern = regexp;
   static std::atomic<uint64_t> next_id{1};
   rp->id = next_id.fetch_add(1);
-  int rc = upload_program(rp.get());
-  if (rc != RJ_OK) return rc;
+  RJ_TRY(upload_program(rp.get()));
   *out = rp.release();
   return RJ_OK;
 }
@@ -1315,8 +1319,7 @@ int rj_scan_create(const rj_program* prog, rj_scan** out) {
   auto s = std::make_unique<rj_scan>();
   s->prog = prog;
   s->timing = default_timing()->load() != 0;
-  int rc = scan_init(s.get());
-  if (rc != RJ_OK) return rc;
+  RJ_TRY(scan_init(s.get()));
   *out = s.release();
   return RJ_OK;
 }
@@ -1344,9 +1347,8 @@ int64_t rj_scan_run(rj_scan* s, const void* d_text, uint64_t n, uint64_t own_beg
                     uint64_t carry_cur, uint64_t carry_prev_end, int have_prev, void* hip_stream) {
   ErrnoGuard errno_guard;
   if (!s) return fail(RJ_BAD_ARGUMENT, "null scan");
-  int rc = run_pipeline(s, static_cast<const uint8_t*>(d_text), n, own_begin, own_end, carry_cur, carry_prev_end,
-                        have_prev, static_cast<hipStream_t>(hip_stream));
-  if (rc != RJ_OK) return rc;
+  RJ_TRY(run_pipeline(s, static_cast<const uint8_t*>(d_text), n, own_begin, own_end, carry_cur, carry_prev_end,
+                        have_prev, static_cast<hipStream_t>(hip_stream)));
   return static_cast<int64_t>(s->result_count);
 }
 
@@ -1389,8 +1391,7 @@ static int scan_start(rj_scan* s, const void* d_text, uint64_t n, void* hip_stre
   const ScanGeometry geo = scan_geometry(std::max<uint64_t>(end_chunk > first_chunk ? end_chunk - first_chunk : 0, 1));
   sp.span_chunks = geo.span_chunks;
   const uint64_t region_cap = std::min<uint64_t>(std::max<uint64_t>(s->region_cap_hint, 64), geo.span_chunks * 1024);
-  int rc = ensure_lists(s, geo.n_regions, static_cast<uint32_t>(region_cap), static_cast<uint64_t>(geo.n_regions) * region_cap);
-  if (rc != RJ_OK) return rc;
+  RJ_TRY(ensure_lists(s, geo.n_regions, static_cast<uint32_t>(region_cap), static_cast<uint64_t>(geo.n_regions) * region_cap));
   RJ_HIP(s->valid_counts.reserve(static_cast<size_t>(geo.n_regions) * sizeof(uint32_t)));
   sp.hits = s->hits.as<uint64_t>();
   sp.region_cap = static_cast<uint32_t>(region_cap);
@@ -1456,8 +1457,7 @@ int64_t rj_scan_finish(rj_scan* s) {
     if (hc[kCntOverflow] != 0)  // size the regions for the fullest one before running again
       s->region_cap_hint = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(hc[kCntMaxRegion] * 2, 256), 1u << 20));
   }
-  int rc = run_pipeline(s, s->pending_text, s->pending_n, 0, s->pending_n + 1, 0, 0, 0, s->pending_stream);
-  if (rc != RJ_OK) return rc;
+  RJ_TRY(run_pipeline(s, s->pending_text, s->pending_n, 0, s->pending_n + 1, 0, 0, 0, s->pending_stream));
   return static_cast<int64_t>(s->result_count);
 }
 
@@ -1522,9 +1522,7 @@ int64_t rj_scan_replace(rj_scan* s, const void* d_text, uint64_t n, const char* 
   launch_replace_gather(static_cast<const uint8_t*>(d_text), n, spans, s->scan_b.as<uint64_t>(), m, s->with_buf.as<uint8_t>(),
                         with_len, static_cast<uint8_t*>(d_out), out_cap, s->long_gaps.as<uint64_t>(),
                         s->counters.as<unsigned long long>(), st);
-  RJ_HIP(hipMemcpyAsync(s->host_counters, s->counters.p, kCntSize * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  RJ_HIP(hipStreamSynchronize(st));
-  RJ_HIP(hipGetLastError());
+  RJ_TRY(read_counters(s, st));
   const uint64_t new_len = s->host_counters[kCntFinal];
   if (new_len > out_cap) return fail(RJ_BAD_ARGUMENT, "replace output needs %llu bytes", static_cast<unsigned long long>(new_len));
   return static_cast<int64_t>(new_len);

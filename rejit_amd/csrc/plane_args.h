@@ -1,7 +1,8 @@
 // rejit_amd/csrc/plane_args.h -- the launch arguments of the plane kernels (plane_scan.hip, plane_count.hip) that are pure
 // arithmetic on a plan and a range: the three encodings of a plan's base windows, the window positions and 2-KiB blocks of
-// the starts [sb, se) and their split over the regions, a pattern's own window range.  Host only, no HIP: multi_pattern.hip
-// fills the kernels' structs from these, tests/test_plane_args.py compiles them with g++.
+// the starts [sb, se) and their split over the regions, a pattern's own window range -- and the chunk range engine.hip's
+// run_range scans.  Host only, no HIP: multi_pattern.hip and engine.hip fill the kernels' structs from these,
+// tests/test_plane_args.py compiles them with g++.
 #pragma once
 
 #include <algorithm>
@@ -71,6 +72,31 @@ inline void window_range(uint64_t n, uint64_t sb, uint64_t se, uint32_t win_offs
   const uint64_t last_w = n >= win_len ? n - win_len + 1 : 0;
   *wlo = sb + win_offset;
   *whi = std::max(std::min<uint64_t>(se + win_offset, last_w), *wlo);
+}
+
+// engine.hip, run_range: what one pattern's scan kernel walks for the starts [sb, se) -- the window positions [wlo, whi), never
+// reversed, and the 1-KiB chunks [first_chunk, end_chunk) that hold them.  A window position w belongs to the starts
+// w - max_offset .. w - min_offset (fixed windows: both are the window's offset; floating ones: float_min and float_max) and
+// has win_len bytes of text behind it; behind an unbounded prefix a start's hit may lie anywhere up to the last position.
+// Dense mode (no windows) walks the chunks of the starts themselves and has no window positions.
+struct ChunkRange {
+  uint64_t wlo = 0, whi = 0, first_chunk = 0, end_chunk = 0;
+  uint64_t chunks() const { return end_chunk > first_chunk ? end_chunk - first_chunk : 0; }
+};
+inline ChunkRange chunk_range(uint64_t n, uint64_t sb, uint64_t se, bool windows, uint32_t min_offset, uint32_t max_offset, uint32_t win_len,
+                              bool behind) {
+  ChunkRange r;
+  if (windows) {
+    const uint64_t last_w = n >= win_len ? n - win_len + 1 : 0;  // a window must fit: w + len <= n
+    r.wlo = sb + min_offset;
+    r.whi = std::max(behind ? last_w : std::min<uint64_t>(se + max_offset, last_w), r.wlo);
+    r.first_chunk = r.wlo / 1024;
+    r.end_chunk = (r.whi + 1023) / 1024;
+  } else {
+    r.first_chunk = sb / 1024;
+    r.end_chunk = (se + 1023) / 1024;
+  }
+  return r;
 }
 
 }  // namespace rejit_amd

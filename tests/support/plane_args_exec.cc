@@ -47,6 +47,16 @@ void pa_window_range(uint64_t n, uint64_t sb, uint64_t se, uint32_t win_offset, 
   window_range(n, sb, se, win_offset, win_len, &out[0], &out[1]);
 }
 
+// out: wlo, whi, first_chunk, end_chunk
+void pa_chunk_range(uint64_t n, uint64_t sb, uint64_t se, int windows, uint32_t min_offset, uint32_t max_offset, uint32_t win_len, int behind,
+                    uint64_t* out) {
+  const ChunkRange r = chunk_range(n, sb, se, windows != 0, min_offset, max_offset, win_len, behind != 0);
+  out[0] = r.wlo;
+  out[1] = r.whi;
+  out[2] = r.first_chunk;
+  out[3] = r.end_chunk;
+}
+
 }  // extern "C"
 
 #ifdef PLANE_ARGS_EXEC_MAIN
@@ -114,6 +124,40 @@ int main() {
               }
             }
   }
+  // the engine's chunk range: fixed (lo_off == hi_off), floating, behind and dense, against the window positions w = s + off
+  // (behind: any w >= sb + lo_off) that have w_len bytes of text, and the 1-KiB chunks that hold them / the starts
+  const uint64_t small[] = {0, 3, 8, 1023, 1024, 1025, 2048 + 7, 3 * 1024 + 1};
+  long with_positions = 0;
+  for (uint64_t n : small) {
+    const uint64_t at[] = {0, 1, 1016, 1023, 1024, 1025, 2047, 2048, n > 0 ? n - 1 : 0, n, n + 1};
+    for (uint64_t sb : at)
+      for (uint64_t se : at)
+        for (uint32_t lo_off : offs)
+          for (uint32_t hi_off : offs)
+            for (uint32_t w_len = 1; w_len <= 8; w_len += 7)
+              for (int form = 0; form < 3; form++, cases++) {   // 0 windows, 1 windows behind a prefix, 2 dense
+                if (sb >= se || se > n + 1 || hi_off < lo_off) continue;
+                uint64_t o[4];
+                pa_chunk_range(n, sb, se, form != 2, lo_off, hi_off, w_len, form == 1, o);
+                uint64_t first = ~0ull, last = 0, count = 0;
+                if (form == 2) {
+                  first = sb, last = se - 1, count = se - sb;
+                  CHECK(o[0] == 0 && o[1] == 0);
+                } else {
+                  for (uint64_t w = sb + lo_off; w + w_len <= n; w++)
+                    if (form == 1 || w < se + hi_off) first = count++ ? first : w, last = w;
+                  CHECK(o[0] == sb + lo_off && o[1] >= o[0] && o[1] - o[0] == count);
+                }
+                // every position has its chunk, no chunk in front of the first position's or behind the last one's
+                if (count) {
+                  CHECK(o[2] == first / 1024 && o[3] == last / 1024 + 1);
+                  with_positions++;
+                } else {
+                  CHECK(o[3] <= o[2] + 1 && o[2] == o[0] / 1024);
+                }
+              }
+  }
+  CHECK(with_positions > 1000);
   std::printf("%ld cases\n", cases);
   return 0;
 }

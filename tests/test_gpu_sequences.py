@@ -464,6 +464,72 @@ def test_want_exact_is_per_call(rj, oracle):
     assert st["exact_path"] >= 1, st
 
 
+# ---------------------------------------------------------------- the list tail (automata of more than 128 positions)
+
+
+def test_list_tail_small_finalize_and_large_path(rj, oracle):
+    """engine.hip, list_tail: an automaton of more than 128 positions (n_words > 4) never takes the one-workgroup kernel nor the
+    in-region tail -- region_offsets, verify_wave, finalize_small; more than kFinalizeCap (2048) candidate slots send the run on
+    to finalize_large (large_path 1), a dozen matches do not (large_path 0).  One object: the hints of each run meet the other."""
+    rx = b"qzvw[a-z]{1,140}"
+    seq = Seq(rj, Want(oracle), rx, seed=11)
+    info = seq.prog.info()
+    assert info["scan_mode"] == 1 and info["n_words"] > 4, info
+    rng = random.Random(11)
+    parts = []
+    while sum(map(len, parts)) < 60000:
+        parts.append(b"qzvw" + bytes(rng.choice(b"abqz") for _ in range(rng.randrange(0, 6))) + rng.choice([b" ", b"\n", b"Q", b"qzv "]))
+    many = b"".join(parts)[:60000]
+    assert many.count(b"qzvw") > 2048 and len(many) <= 64 << 10
+    few = alphabet_maker(b"abcqzvw \n", 12, b"qzvwabc ", 5000)(60000)
+    assert 10 <= len(seq.want.all(rx, few)) <= 40
+    for text, name, large in ((many, "many", 1), (few, "few", 0), (many, "many", 1), (few, "few", 0)):
+        st = seq.step("run", text, name=name)
+        assert st["large_path"] == large and st["n_matches"] == len(seq.want.all(rx, text)), (name, st)
+    seq.step("halves", many, 20011, name="many")
+    seq.step("tail", few, 30001, name="few")
+
+
+def _floating_wide(rj):
+    rx = b"(ab|b){2,5}xyz[ab]{1,140}"
+    info = rj.Program(rx).info()
+    # windows mode, more than 128 positions, and floating: the window `xyz` sits behind 2..10 bytes of prefix (offset 0 with a
+    # match longer than the window is how info() shows it, as in test_no_local_select_floating_windows)
+    assert info["scan_mode"] == 1 and info["n_words"] > 4 and info["window_offset"] == 0 and info["min_len"] != info["window_len"], info
+    return rx
+
+
+def test_floating_windows_on_the_list_tail_read_their_hit_count(rj, oracle):
+    """engine.hip, list_tail: floating windows of an automaton too wide for the regions (expand > 1, no floating_regions) -- the
+    run reads the hit count between the scan and the verify kernel, which sizes the candidate slots.  A few hundred hits, twice
+    on one object: cold hints and warm ones; hits x 9 possible starts are more than finalize_small takes (large_path 1: the
+    sort of the interleaved starts)."""
+    rx = _floating_wide(rj)
+    text = alphabet_maker(b"ab c\n", 13, b"babxyzab", 600)(200000)
+    t = bytearray(text)
+    for at in range(150, len(t) - 8, 4100):
+        t[at:at + 8] = b" xyzabab"          # a hit without its prefix, and `bbabxyz` chains
+    text = bytes(t)
+    assert 300 <= text.count(b"xyz") <= 999 and len(text) <= 256 << 10
+    seq = Seq(rj, Want(oracle), rx, seed=13)
+    for name in ("cold", "warm"):
+        st = seq.step("run", text, name=name)
+        assert st["large_path"] == 1 and st["n_hits"] == text.count(b"xyz"), (name, st)
+    seq.step("halves", text, 70001, name="warm")
+
+
+def test_floating_windows_on_the_list_tail_grow_their_candidate_slots(rj, oracle):
+    """The same route with more candidate slots than the lists start with (65536): they grow between the scan and the verify
+    kernel, on the cold run; the warm run finds them grown."""
+    rx = _floating_wide(rj)
+    text = alphabet_maker(b"ab c\n", 14, b"abxyzb ", 24)(240000)
+    assert text.count(b"xyz") * 9 > 65536 and len(text) <= 256 << 10
+    seq = Seq(rj, Want(oracle), rx, seed=14)
+    for name in ("cold", "warm"):
+        st = seq.step("run", text, name=name)
+        assert st["large_path"] == 1 and st["n_hits"] == text.count(b"xyz"), (name, st)
+
+
 # ---------------------------------------------------------------- host entries and their cached scans
 
 

@@ -1,7 +1,8 @@
 """CPU test of the pure launch-argument builders of the plane kernels (rejit_amd/csrc/plane_args.h, used by
 multi_pattern.hip for plane_scan / plane_list / plane_count and their general forms): the three encodings of a plan's base
 windows against ONE definition of the 2-bit symbol code, the window positions and 2-KiB blocks of a range of starts and their
-split over the regions against brute force, a pattern's own window range.  The driver (tests/support/plane_args_exec.cc)
+split over the regions against brute force, a pattern's own window range, and the chunk range engine.hip's run_range scans
+(chunk_range) against the window sweep's restatement of it.  The driver (tests/support/plane_args_exec.cc)
 is loaded through ctypes, and once more built as a stand-alone program under the address and undefined sanitizers."""
 import ctypes
 import os
@@ -10,6 +11,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+import window_sweep as W
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -40,6 +43,8 @@ def pa():
     lib.pa_split.argtypes = [U64, U64, U32, u64p]
     lib.pa_window_range.restype = None
     lib.pa_window_range.argtypes = [U64, U64, U64, U32, U32, u64p]
+    lib.pa_chunk_range.restype = None
+    lib.pa_chunk_range.argtypes = [U64, U64, U64, ctypes.c_int, U32, U32, U32, ctypes.c_int, u64p]
     return lib
 
 
@@ -120,6 +125,46 @@ def test_a_patterns_own_window_range(pa):
                         w = [s + off for s in range(sb, se) if s + off + length <= n]
                         assert out[1] >= out[0] == sb + off, (n, sb, se, off, length)
                         assert out[1] - out[0] == len(w), (n, sb, se, off, length)
+
+
+def test_the_engines_chunk_range_on_the_window_sweeps_geometries(pa):
+    """chunk_range is what run_range scans; tests/window_sweep.py plans its texts from window_range, its own statement of the
+    same four values.  Every plan of the sweep -- whole texts of every family, own ranges, the tails with the window behind an
+    unbounded prefix -- must get the same (wlo, whi, first_chunk, end_chunk) from both; a sweep that plans nothing fails."""
+    out = (U64 * 4)()
+    checked = {False: 0, True: 0}
+    for sweep in list(W.FAMILIES) + ["own"] + list(W.TAILS):
+        behind = bool(W.TAILS[sweep]["behind"]) if sweep in W.TAILS else False
+        for grid in W.GRIDS:
+            for case in W.cases_of(sweep, grid):
+                plan = case.plan
+                offset, length = plan.window
+                pa.pa_chunk_range(plan.n, plan.sb, plan.se, 1, offset, offset, length, int(behind), out)
+                assert tuple(out) == (plan.wlo, plan.whi, plan.first_chunk, plan.end_chunk), (case.label, tuple(out))
+                assert tuple(out) == W.window_range(plan.n, plan.sb, plan.se, offset, length, behind), case.label
+                checked[behind] += 1
+    assert checked[False] > 500 and checked[True] > 0, checked      # fixed windows (own ranges among them) and behind
+
+
+def test_chunk_range_floating_and_dense(pa):
+    """The two forms the sweep does not plan: floating windows (w in [s + float_min, s + float_max]) are the fixed form with the
+    two offsets apart, dense mode walks the chunks of the starts themselves."""
+    out = (U64 * 4)()
+    checked = 0
+    for n in (0, 7, 1023, 1024, 1025, 4096 + 5, 10 ** 5):
+        for sb in _starts(n):
+            for se in [e for e in _starts(n) if e > sb]:
+                pa.pa_chunk_range(n, sb, se, 0, 3, 7, 4, 0, out)
+                assert tuple(out) == (0, 0, sb // 1024, (se + 1023) // 1024), (n, sb, se)
+                for fmin, fmax in ((0, 3), (2, 7), (5, 5)):
+                    pa.pa_chunk_range(n, sb, se, 1, fmin, fmax, 4, 0, out)
+                    w = np.arange(sb + fmin, se + fmax, dtype=np.int64)                       # brute force, as for the blocks above
+                    w = w[w + 4 <= n]
+                    want = (w[0], w[-1] + 1) if len(w) else (sb + fmin, sb + fmin)
+                    assert (out[0], out[1]) == want, (n, sb, se, fmin, fmax)
+                    assert (out[2], out[3]) == (out[0] // 1024, (out[1] + 1023) // 1024), (n, sb, se, fmin, fmax)
+                    checked += 1
+    assert checked > 300
 
 
 def test_the_driver_is_clean_under_the_address_and_undefined_sanitizers():

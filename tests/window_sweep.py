@@ -73,7 +73,7 @@ RANK = _Rank()
 
 # ------------------------------------------------------------------------------------------------ the arithmetic
 def window_range(n, sb, se, offset, length, behind=False):
-    """engine.hip, run_range -> (wlo, whi, first_chunk, end_chunk); a behind pattern reaches last_w"""
+    """plane_args.h, chunk_range (engine.hip: run_range) -> (wlo, whi, first_chunk, end_chunk); a behind pattern reaches last_w"""
     last_w = n - length + 1 if n >= length else 0
     wlo = sb + offset
     whi = last_w if behind else min(se + offset, last_w)
