@@ -563,16 +563,17 @@ static int run_streams(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t s
   return 0;
 }
 
-// RunParams of the matches that begin in [sb, se) and are looked for from min_start on, over the scan's own buffers.
-static int run_params(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, uint64_t min_start, RunParams* a) {
+// RunParams of the matches that begin in [sb, se) and are looked for from min_start on, over the scan's own buffers; the tiles
+// begin with the one that holds scan_from <= min_start.
+static int run_params(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, uint64_t min_start, uint64_t scan_from, RunParams* a) {
   a->text = d_text;
   a->n = n;
   a->sb = sb;
   a->se = se;
   a->min_start = min_start;
   a->plan = s->prog->run;
-  a->tile_bytes = run_tile_bytes(n - std::min<uint64_t>(min_start, n));
-  a->n_tiles = run_tiles(min_start, n, a->tile_bytes, &a->first_tile);
+  a->tile_bytes = run_tile_bytes(n - std::min<uint64_t>(scan_from, n));
+  a->n_tiles = run_tiles(scan_from, n, a->tile_bytes, &a->first_tile);
   RJ_HIP(s->run_summaries.reserve(sizeof(RunSummary) * run_resolve_slots(a->n_tiles)));
   RJ_HIP(s->run_tile_in.reserve(sizeof(RunTileIn) * run_resolve_slots(a->n_tiles)));
   a->summaries = s->run_summaries.as<RunSummary>();
@@ -628,7 +629,11 @@ static int run_runs(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, 
   const uint64_t lag = rp->run.lag;
   RunParams a{};
   // (a match consumes at least one byte: none begins at n)
-  RJ_TRY(run_params(s, d_text, n, sb + lag, std::min<uint64_t>(se, n) + lag, std::max<uint64_t>(sb, have_prev ? carry_cur : 0) + lag, &a));
+  const uint64_t min_start = std::max<uint64_t>(sb, have_prev ? carry_cur : 0) + lag;
+  // (a blocked segment stays blocked up to its break, which may lie before min_start: the kernels read from the tile of the
+  // carried match's last byte on, so that a break between that match and the own range lifts the block)
+  const uint64_t scan_from = blocked_in ? std::min<uint64_t>(min_start, carry_prev_end - 1) : min_start;
+  RJ_TRY(run_params(s, d_text, n, sb + lag, std::min<uint64_t>(se, n) + lag, min_start, scan_from, &a));
   a.blocked_in = blocked_in;
   // (`^` in front of the shape is a mask on the kernels' start stream, `$` behind it a test of the closing break: run_scan.hip)
   // MatchAllCount of the whole text: one pass over it
@@ -641,7 +646,7 @@ static int run_runs(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, 
 static int run_pairs(rj_scan* s, const uint8_t* d_text, uint64_t n, uint64_t sb, uint64_t se, hipStream_t st) {
   if (!s->prog->run.pair || sb != 0 || se < n || n == 0) return 0;
   RunParams a{};
-  RJ_TRY(run_params(s, d_text, n, 0, n, 0, &a));
+  RJ_TRY(run_params(s, d_text, n, 0, n, 0, 0, &a));
   return run_three_steps(s, a, true, s->count_only_run, st);
 }
 

@@ -1017,14 +1017,34 @@ static uint64_t forced_block_tiles() {
   }();
   return v;
 }
+// the resolve's shape for n_tiles tiles: the tiles per block of the two-level form, and whether one workgroup (1) or the two
+// levels (2) resolve them
+static int resolve_levels(uint64_t n_tiles, uint64_t* block_tiles) {
+  *block_tiles = forced_block_tiles() ? forced_block_tiles() : kBlockTiles;
+  return (n_tiles <= kOneLevelTiles && !forced_block_tiles()) ? 1 : 2;
+}
 uint64_t run_resolve_slots(uint64_t n_tiles) {
-  const uint64_t bt = forced_block_tiles() ? forced_block_tiles() : kBlockTiles;
+  uint64_t bt;
+  resolve_levels(n_tiles, &bt);
   return n_tiles + (n_tiles + bt - 1) / bt;
+}
+// TEST SUPPORT (tests/run_sweep.py; in no public header): the geometry a run or pair launch over a text of n bytes, looked at
+// from min_start on, gets from the functions above and the overrides they read -- out[0..4] = tile_bytes, first_tile, n_tiles,
+// block_tiles, levels of the resolve.  Host arithmetic only.
+extern "C" void rj_test_run_geometry(uint64_t n, uint64_t min_start, uint64_t* out) {
+  const uint64_t tile_bytes = run_tile_bytes(n - (min_start < n ? min_start : n));   // (as run_params, engine.hip)
+  uint64_t first_tile = 0, block_tiles = 0;
+  const uint64_t n_tiles = run_tiles(min_start, n, tile_bytes, &first_tile);
+  const int levels = resolve_levels(n_tiles, &block_tiles);
+  out[0] = tile_bytes;
+  out[1] = first_tile;
+  out[2] = n_tiles;
+  out[3] = block_tiles;
+  out[4] = static_cast<uint64_t>(levels);
 }
 void launch_run_resolve(const RunParams& a0, hipStream_t st) {
   RunParams a = a0;
-  a.block_tiles = forced_block_tiles() ? forced_block_tiles() : kBlockTiles;
-  if (a.n_tiles <= kOneLevelTiles && !forced_block_tiles()) {
+  if (resolve_levels(a.n_tiles, &a.block_tiles) == 1) {
     hipLaunchKernelGGL(run_resolve, dim3(1), dim3(1024), 0, st, a);
     return;
   }
@@ -1063,8 +1083,7 @@ void launch_pair_summary(const RunParams& a, hipEvent_t t0, hipEvent_t t1, hipSt
 }
 void launch_pair_resolve(const RunParams& a0, hipStream_t st) {
   RunParams a = a0;
-  a.block_tiles = forced_block_tiles() ? forced_block_tiles() : kBlockTiles;
-  if (a.n_tiles <= kOneLevelTiles && !forced_block_tiles()) {
+  if (resolve_levels(a.n_tiles, &a.block_tiles) == 1) {
     hipLaunchKernelGGL(pair_resolve, dim3(1), dim3(1024), 0, st, a);
     return;
   }

@@ -488,6 +488,18 @@ long pe_run_match_all(const char* re, const uint8_t* text, uint64_t n, uint64_t*
   return static_cast<long>(k);
 }
 
+// make_run_plan's decisions for a pattern, as the launches of run_scan.hip read them (tests/test_run_sweep_plan.py: which kernel
+// instantiation and which flags a sweep family reaches): info[0..10] = ok, pair, has_b, n_ranges, lag, bol, eol, a_neg, l_neg, b_neg,
+// high_half.  0, or a negative lowering status.
+int pe_run_plan(const char* re, uint32_t* info) {
+  LowerResult lr = lower(re);
+  if (lr.status != 0) return lr.status;
+  const RunPlan pl = make_run_plan(*lr.program);
+  const uint32_t v[11] = {pl.ok, pl.pair, pl.has_b, pl.n_ranges, pl.lag, pl.bol, pl.eol, pl.a_neg, pl.l_neg, pl.b_neg, pl.high_half};
+  memcpy(info, v, sizeof(v));
+  return 0;
+}
+
 // The PAIR shape of run_scan.h (`"[^"]*"`: the same class Q at both ends, no Q inside L) on the CPU: the plan's class encoding and the
 // rule the pair kernels implement -- the matches are the pairs (1st, 2nd), (3rd, 4th) ... of the Q bytes since the last RESET (a
 // break that is no Q; the text's end) -- walked byte by byte.  -101: the pattern does not have the shape.
