@@ -314,6 +314,34 @@ int64_t rj_scan_records_split(rj_scan* scan, uint64_t n, const uint64_t* d_rec_b
                               uint64_t n_records, const uint32_t* d_counts, const uint64_t* d_first,
                               const uint64_t* d_indices, uint64_t n_indices, int what, uint64_t* d_piece_first,
                               uint64_t* d_piece_begin, uint64_t* d_piece_end, uint64_t piece_cap, void* hip_stream);
+/* The rows of a record table GROUPED BY THEIR BYTES (rejit_amd/csrc/record_group.hip): which records are
+ * equal -- `sort | uniq -c`, `awk '{c[$3]++}'`, Arrow's dictionary_encode / unique / value_counts over a string column -- exactly
+ * (lengths and bytes are compared; a hash only finds the candidates) and deterministically, without a download.  Any record
+ * table over the text serves: rj_scan_records_split's pieces (matches, fields), lines, the strings of a column.  k, r(j) and
+ * d_indices are those of rj_scan_records_pack: any order, repeats allowed, non-NULL with n_indices == 0 is no rows.  Row j is
+ * the byte string text[rec_begin[r(j)], rec_end[r(j)]); two rows are equal when their lengths and bytes are; empty rows are
+ * equal to each other; a row's identity is j, not r(j).  With the distinct strings numbered g = 0 .. G - 1 in order of first
+ * appearance:
+ *     d_group[j]       = the group of row j                              (k uint64, may be NULL)
+ *     d_rep[g]         = the smallest j with that string, so strictly ascending       (group_cap uint64)
+ *     d_group_count[g] = the number of rows in group g; the counts add up to k        (group_cap uint64)
+ * d_group are the indices of a dictionary encoding, the dictionary is rj_scan_records_pack over the rows d_rep (composed with
+ * d_indices when there are any).  Returns G WHATEVER group_cap is and never writes d_rep / d_group_count at or beyond
+ * group_cap; d_rep == d_group_count == NULL with group_cap == 0 is the size query (d_group is still written when given).
+ * With G <= group_cap every row of the three tables is written exactly once, nothing has to be cleared first, nothing behind
+ * G or k is touched.  k == 0 returns 0.  The scan lends scratch only (44 to 68 bytes per row): spans, stats and the state of
+ * its last rj_scan_records (rj_scan_records_select included) stay as they were.  One synchronise per call.
+ * Refusals (RJ_BAD_ARGUMENT; one that names a row gives the first bad j as "row <j> "; a refused call writes no output row and
+ * is never led outside the text or a table): an index >= n_records; a row without begin <= end <= n; a null argument (d_text
+ * with n > 0, the tables with n_records > 0, d_rep or d_group_count with group_cap > 0); a table that is not 8-byte aligned.
+ * k >= 2^31: RJ_TOO_LARGE (rows and slots share 32-bit words in the scratch).
+ * Two knobs for tests, read from the environment at every call: RJ_GROUP_HASH_BITS=b keeps only the low b bits of every hash
+ * (different strings then share probe chains: the byte compare decides), RJ_GROUP_LONG_BYTES=L moves the length above which
+ * a row is walked by a wave instead of a lane (default 64). */
+int64_t rj_scan_records_group(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                              const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
+                              uint64_t* d_group, uint64_t* d_rep, uint64_t* d_group_count, uint64_t group_cap,
+                              void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

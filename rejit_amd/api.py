@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_split.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_split.h", "record_group.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -195,7 +195,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group"]
 
 
 def load_library():
@@ -303,6 +303,8 @@ def load_library():
     L.rj_scan_records_replace.argtypes = [vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, cp, u64, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
     L.rj_scan_records_split.restype = i64
     L.rj_scan_records_split.argtypes = [vp, u64, vp, vp, u64, vp, vp, vp, u64, ctypes.c_int, vp, vp, vp, u64, vp]
+    L.rj_scan_records_group.restype = i64
+    L.rj_scan_records_group.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp]
     _lib = L
     return L
 
@@ -754,6 +756,42 @@ class Scan:
         if total:
             call(piece_begin, piece_end, total)
         return piece_begin, piece_end, piece_first
+
+    def group_records(self, text_tensor, rec_begin, rec_end, indices=None, stream=None):
+        """rj_scan_records_group: the rows text[rec_begin[i], rec_end[i]) -- all of them, or those `indices` names, as
+        pack_records' -- grouped by their bytes, exactly: Arrow's dictionary_encode / value_counts, `sort | uniq -c` in order of
+        first appearance.  Returns (group, rep, count), int64 device tensors: group[j] is the group of row j (k entries), rep[g]
+        the smallest row with group g's string (strictly ascending) and count[g] the number of its rows (G entries each).  The
+        dictionary is pack_records over the rows rep (indices[rep] when there are indices); records.top_groups picks the most
+        frequent.  ONE size query (which writes `group` already), exactly G rows allocated.  RejitError (RJ_BAD_ARGUMENT,
+        naming the first bad row) for a bad index or row.  The scan's spans, stats and select_records stay as they were."""
+        import torch
+
+        t = text_tensor
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        n_records = int(rec_begin.numel())
+        for x in (rec_begin, rec_end):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
+        else:
+            k = n_records
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        group = torch.empty(k, dtype=torch.int64, device=t.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+
+        def call(g, rep, count, cap):
+            return int(_check(self._lib.rj_scan_records_group(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k,
+                                                              ptr(g), ptr(rep) if cap else None, ptr(count) if cap else None, cap, ctypes.c_void_p(st))))
+        total = call(group, None, None, 0)
+        rep = torch.empty(total, dtype=torch.int64, device=t.device)
+        count = torch.empty(total, dtype=torch.int64, device=t.device)
+        if total:
+            call(None, rep, count, total)
+        return group, rep, count
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""

@@ -99,3 +99,13 @@ def nonempty_pieces(piece_begin, piece_end):
     import torch
 
     return torch.nonzero(piece_end > piece_begin).reshape(-1).contiguous()
+
+
+def top_groups(count, rep, top: int):
+    """(count, rep, group) of the `top` most frequent groups of Scan.group_records: by descending count, ties in order of
+    first appearance (a stable sort over the G groups: `sort -rn | head` over `uniq -c`).  group: the groups' numbers."""
+    import torch
+
+    _, order = torch.sort(count, descending=True, stable=True)
+    order = order[:max(int(top), 0)].contiguous()
+    return count[order].contiguous(), rep[order].contiguous(), order

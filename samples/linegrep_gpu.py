@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K]] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -19,6 +19,10 @@ answer on the GPU:
   -f N   PATTERN is the field separator: print field N (1-based) of every line -- with -p / -v: of every selected line --, an
        empty line where a line has fewer fields (`awk -F PATTERN '{print $N}'`): the fields are rj_scan_records_split's pieces
        between the matches, field N of every row a torch gather over its offsets, the packed fields the only download
+  -u   with -o or -f N: print each DISTINCT match or field once, in order of first appearance, with the number of its
+       occurrences in front as "%7d %s" (`... | sort | uniq -c` without the sort's order): rj_scan_records_group groups the pieces
+       by their bytes on the device; only the packed dictionary and the counts come back
+  -t K   with -u: only the K most frequent, by descending count, ties in order of first appearance (`| sort -rn | head -K`)
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -39,11 +43,16 @@ def main(argv):
     if "-f" in argv[:-1]:
         at = argv.index("-f")
         field, argv = argv[at + 1], argv[:at] + argv[at + 2:]
-    matches_out = "-o" in argv
-    argv = [a for a in argv if a != "-o"]
+    top = None
+    if "-t" in argv[:-1]:
+        at = argv.index("-t")
+        top, argv = argv[at + 1], argv[:at] + argv[at + 2:]
+    matches_out, unique = "-o" in argv, "-u" in argv
+    argv = [a for a in argv if a not in ("-o", "-u")]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
-    if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)):
+    if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)) or (top is not None and (not top.isdigit() or not unique)) or (
+            unique and not matches_out and field is None):
         sys.stderr.write(__doc__)
         return 2
     path, pattern = rest
@@ -91,7 +100,15 @@ def main(argv):
             else:
                 pb, pe, _ = records.field_records(pb, pe, pf, int(field) - 1)
                 keep = None
-            if keep is None or keep.numel():
+            if unique and (keep is None or keep.numel()):
+                _, rep, count = scan.group_records(text, pb, pe, indices=keep)
+                if top is not None:
+                    count, rep, _ = records.top_groups(count, rep, int(top))
+                packed, _, _ = scan.pack_records(text, pb, pe, indices=rep if keep is None else keep[rep], fill=10, lead=0, gap=1)
+                words = packed.cpu().numpy().tobytes().split(b"\n")     # the dictionary and the counts: the only downloads
+                sys.stdout.flush()
+                sys.stdout.buffer.write(b"".join(b"%7d %s\n" % (c, w) for c, w in zip(count.cpu().tolist(), words)))
+            elif keep is None or keep.numel():
                 packed, _, _ = scan.pack_records(text, pb, pe, indices=keep, fill=10, lead=0, gap=1)
                 sys.stdout.flush()
                 sys.stdout.buffer.write(packed.cpu().numpy().tobytes())   # the only download besides the summary
