@@ -342,6 +342,38 @@ int64_t rj_scan_records_group(rj_scan* scan, const void* d_text, uint64_t n, con
                               const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
                               uint64_t* d_group, uint64_t* d_rep, uint64_t* d_group_count, uint64_t group_cap,
                               void* hip_stream);
+/* The rows of a record table IN THE ORDER OF THEIR BYTES (rejit_amd/csrc/record_sort.hip): `sort`,
+ * ORDER BY over a string column, a sorted dictionary, the input of a merge join -- and, over the rows d_rep of
+ * rj_scan_records_group, `sort -u` and `sort | uniq -c` -- exactly, without a download.  k, r(j) and d_indices are those of
+ * rj_scan_records_pack and rj_scan_records_group: any order, repeats allowed, non-NULL with n_indices == 0 is no rows; a row's
+ * identity is j, not r(j).  Row j is the byte string text[rec_begin[r(j)], rec_end[r(j)]).  d_order (k uint64) receives THE
+ * permutation of 0 .. k - 1 with row(order[i]) <= row(order[i + 1]):
+ *     bytes compare as unsigned values (memcmp, `LC_ALL=C sort`);  a proper prefix sorts before the longer row;
+ *     rows with equal bytes come in ascending j (the sort is stable).
+ * The answer is unique and depends on the rows alone; rj_scan_records_pack with d_order as its index list (composed with
+ * d_indices when there are any) prints the sorted table.  Returns k.  Every row of d_order is written exactly once, nothing
+ * has to be cleared first, nothing behind k is touched.  k == 0 returns 0.  The scan lends scratch only (63 bytes per row and
+ * the radix sort's temporary storage): spans, stats and the state of its last rj_scan_records (rj_scan_records_select
+ * included) stay as they were.  One synchronise per refinement round: a round reads 7 more bytes of every row that still
+ * shares everything read so far with another one, behind the prefix ALL rows of such a segment share (skipped from the
+ * second round on); at most G + 1 rounds for G distinct strings, 1 to 3 on columns of short strings.
+ * `stats` (may be NULL) receives what the call did.
+ * Refusals (RJ_BAD_ARGUMENT; one that names a row gives the first bad j as "row <j> "; a refused call writes no output row and
+ * is never led outside the text or a table): an index >= n_records; a row without begin <= end <= n; a null argument (d_text
+ * with n > 0, the tables with n_records > 0, d_order with k > 0); a table that is not 8-byte aligned.
+ * k >= 2^31: RJ_TOO_LARGE (rows and segments share 32-bit words in the scratch).
+ * Two knobs for tests, read from the environment at every call: RJ_SORT_SKIP=0 turns the prefix skip off (7 bytes per round,
+ * whatever the rows share), RJ_SORT_LONG_BYTES=L moves the number of bytes a lane compares before it hands the row to a wave
+ * (default 64). */
+typedef struct {
+  uint64_t rounds;     /* refinement rounds run (0 when k < 2)                          */
+  uint64_t keyed_rows; /* rows given a key, summed over the rounds                      */
+  uint64_t skip_rows;  /* rows compared against their segment's head by the prefix skip */
+  uint64_t long_rows;  /* of those, rows handed to the wave tier                        */
+} rj_sort_stats;
+int64_t rj_scan_records_sort(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                             const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
+                             uint64_t* d_order, rj_sort_stats* stats /* may be NULL */, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_split.h", "record_group.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_split.h", "record_group.h", "record_sort.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -161,6 +161,10 @@ class _RecordStats(ctypes.Structure):
     _fields_ = [("n_kept", ctypes.c_uint64), ("n_matching", ctypes.c_uint64), ("n_crossing", ctypes.c_uint64), ("n_matches", ctypes.c_uint64)]
 
 
+class _SortStats(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_uint64), ("keyed_rows", ctypes.c_uint64), ("skip_rows", ctypes.c_uint64), ("long_rows", ctypes.c_uint64)]
+
+
 class RecordsResult:
     """What Scan.run_records returns: rj_record_stats (n_kept, n_matching, n_crossing, n_matches) and the per-record tensors --
     counts (int32: the library's uint32, saturating, so 2^32 - 1 reads -1) and first (int64), both on the text's device.
@@ -195,7 +199,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort"]
 
 
 def load_library():
@@ -305,6 +309,8 @@ def load_library():
     L.rj_scan_records_split.argtypes = [vp, u64, vp, vp, u64, vp, vp, vp, u64, ctypes.c_int, vp, vp, vp, u64, vp]
     L.rj_scan_records_group.restype = i64
     L.rj_scan_records_group.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp]
+    L.rj_scan_records_sort.restype = i64
+    L.rj_scan_records_sort.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, ctypes.POINTER(_SortStats), vp]
     _lib = L
     return L
 
@@ -792,6 +798,39 @@ class Scan:
         if total:
             call(None, rep, count, total)
         return group, rep, count
+
+    def sort_records(self, text_tensor, rec_begin, rec_end, indices=None, stream=None, stats=False):
+        """rj_scan_records_sort: the rows text[rec_begin[i], rec_end[i]) -- all of them, or those `indices` names, as
+        pack_records' -- in the order of their bytes: unsigned bytes as memcmp and `LC_ALL=C sort` compare them, a proper
+        prefix first, equal rows in ascending row number (stable).  Returns `order`, an int64 device tensor of k entries: THE
+        permutation with row(order[i]) <= row(order[i + 1]); pack_records(..., indices=order) (indices[order] when there are
+        indices) prints the sorted table, torch.flip(order, [0]) is the descending order.  With stats=True returns (order,
+        {"rounds", "keyed_rows", "skip_rows", "long_rows"}).  records.sorted_groups sorts the distinct rows and their counts.
+        RejitError (RJ_BAD_ARGUMENT, naming the first bad row) for a bad index or row.  The scan's spans, stats and
+        select_records stay as they were."""
+        import torch
+
+        t = text_tensor
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        n_records = int(rec_begin.numel())
+        for x in (rec_begin, rec_end):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
+        else:
+            k = n_records
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        order = torch.empty(k, dtype=torch.int64, device=t.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        out = _SortStats()
+        _check(self._lib.rj_scan_records_sort(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k, ptr(order),
+                                              ctypes.byref(out), ctypes.c_void_p(st)))
+        if stats:
+            return order, {f: int(getattr(out, f)) for f, _ in _SortStats._fields_}
+        return order
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""

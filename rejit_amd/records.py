@@ -109,3 +109,18 @@ def top_groups(count, rep, top: int):
     _, order = torch.sort(count, descending=True, stable=True)
     order = order[:max(int(top), 0)].contiguous()
     return count[order].contiguous(), rep[order].contiguous(), order
+
+
+def sorted_groups(scan, text, rec_begin, rec_end, indices=None):
+    """Scan.group_records followed by Scan.sort_records over the distinct rows: (rep_sorted, count_sorted, group_sorted).
+    rep_sorted is the dictionary in byte order (`sort -u`; pack_records over the rows rep_sorted, indices[rep_sorted] when
+    there are indices, prints it), count_sorted its counts (`sort | uniq -c`), group_sorted[j] row j's number in that order
+    -- a dictionary encoding whose codes compare as the strings do.  The sort sees G rows, not k."""
+    import torch
+
+    group, rep, count = scan.group_records(text, rec_begin, rec_end, indices=indices)
+    rows = rep if indices is None else indices[rep].contiguous()
+    order = scan.sort_records(text, rec_begin, rec_end, indices=rows)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.numel(), dtype=torch.int64, device=order.device)
+    return rep[order].contiguous(), count[order].contiguous(), rank[group].contiguous()

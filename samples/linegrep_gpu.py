@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K]] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K]] [-b] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -23,6 +23,9 @@ answer on the GPU:
        occurrences in front as "%7d %s" (`... | sort | uniq -c` without the sort's order): rj_scan_records_group groups the pieces
        by their bytes on the device; only the packed dictionary and the counts come back
   -t K   with -u: only the K most frequent, by descending count, ties in order of first appearance (`| sort -rn | head -K`)
+  -b   byte order (`LC_ALL=C sort`), made on the device by rj_scan_records_sort: with -u the distinct values print in the
+       order of their bytes with their counts (`... | sort | uniq -c`; with -t K the K most frequent, ties in byte order);
+       with -p, -o or -f N and no -u the selected lines, the matches or the fields print sorted (`... | sort`)
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -47,12 +50,12 @@ def main(argv):
     if "-t" in argv[:-1]:
         at = argv.index("-t")
         top, argv = argv[at + 1], argv[:at] + argv[at + 2:]
-    matches_out, unique = "-o" in argv, "-u" in argv
-    argv = [a for a in argv if a not in ("-o", "-u")]
+    matches_out, unique, byte_order = "-o" in argv, "-u" in argv, "-b" in argv
+    argv = [a for a in argv if a not in ("-o", "-u", "-b")]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
     if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)) or (top is not None and (not top.isdigit() or not unique)) or (
-            unique and not matches_out and field is None):
+            unique and not matches_out and field is None) or (byte_order and not matches_out and field is None and "-p" not in flags):
         sys.stderr.write(__doc__)
         return 2
     path, pattern = rest
@@ -101,7 +104,10 @@ def main(argv):
                 pb, pe, _ = records.field_records(pb, pe, pf, int(field) - 1)
                 keep = None
             if unique and (keep is None or keep.numel()):
-                _, rep, count = scan.group_records(text, pb, pe, indices=keep)
+                if byte_order:
+                    rep, count, _ = records.sorted_groups(scan, text, pb, pe, indices=keep)
+                else:
+                    _, rep, count = scan.group_records(text, pb, pe, indices=keep)
                 if top is not None:
                     count, rep, _ = records.top_groups(count, rep, int(top))
                 packed, _, _ = scan.pack_records(text, pb, pe, indices=rep if keep is None else keep[rep], fill=10, lead=0, gap=1)
@@ -109,6 +115,9 @@ def main(argv):
                 sys.stdout.flush()
                 sys.stdout.buffer.write(b"".join(b"%7d %s\n" % (c, w) for c, w in zip(count.cpu().tolist(), words)))
             elif keep is None or keep.numel():
+                if byte_order:
+                    order = scan.sort_records(text, pb, pe, indices=keep)
+                    keep = order if keep is None else keep[order].contiguous()
                 packed, _, _ = scan.pack_records(text, pb, pe, indices=keep, fill=10, lead=0, gap=1)
                 sys.stdout.flush()
                 sys.stdout.buffer.write(packed.cpu().numpy().tobytes())   # the only download besides the summary
@@ -119,6 +128,8 @@ def main(argv):
     elif lines_out:
         if selected:
             lines = scan.select_records(invert=invert)
+            if byte_order:
+                lines = lines[scan.sort_records(text, begins, ends, indices=lines)].contiguous()
             packed, _, _ = scan.pack_records(text, begins, ends, indices=lines, fill=10, lead=0, gap=1)
             sys.stdout.flush()
             sys.stdout.buffer.write(packed.cpu().numpy().tobytes())   # the only download besides the summary
