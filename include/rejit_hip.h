@@ -73,7 +73,8 @@ typedef struct {
   uint64_t n_hits;         /* candidate starts produced by the scan kernel           */
   uint64_t n_candidates;   /* verified (begin,end) candidates before selection       */
   uint64_t n_matches;      /* final left-most-longest, non-overlapping matches       */
-  float scan_ms;           /* start-to-end time of the scan kernel(s), from their dispatch timestamps */
+  float scan_ms;           /* start-to-end time of the scan kernel(s), from their dispatch timestamps (count_path 1: first
+                              workgroup's entry to last workgroup's exit by the device's wall clock, see rj_scan_set_timing) */
   float total_ms;          /* host clock: first launch to final synchronise of the run */
   int32_t retries;         /* runs repeated because a device list had to grow        */
   int32_t large_path;      /* 1 when the rocPRIM sort path was taken                 */
@@ -165,7 +166,12 @@ void rj_scan_destroy(rj_scan* scan);
  * 32 KB .. 16 MiB; ~6.5 us between two kernels of the regexdna step).  So it is OFF unless asked for -- per object, or for
  * every object created from now on (rj_set_default_timing returns the previous default; environment RJ_KERNEL_TIMING=1 sets
  * the initial one) -- and scan_ms reads 0 without it.  The Python binding (rejit_amd/api.py: bench.py, the tests and the
- * tools read scan_ms) switches the default on when it loads the library. */
+ * tools read scan_ms) switches the default on when it loads the library.
+ * The one-kernel counts path (rj_multi_set_counts_only, rj_scan_count, rj_match_all(..., NULL) with count_path == 1) takes
+ * no start event: there scan_ms runs from the first workgroup's entry into the kernel to the last workgroup's exit, read from
+ * the device's constant-rate wall clock (100 MHz on gfx950: 10 ns resolution; hipDeviceAttributeWallClockRate) by the kernel
+ * itself.  That costs nothing on the stream, timing on or off.  Every other path -- and a counts run that was void and was
+ * answered by the span pipeline -- still uses the events. */
 int rj_scan_set_timing(rj_scan* scan, int on);
 int rj_set_default_timing(int on);
 int64_t rj_scan_run(rj_scan* scan, const void* d_text, uint64_t n, uint64_t own_begin, uint64_t own_end,
@@ -426,7 +432,8 @@ int rj_multi_set_tail_stream(rj_multi* multi, int on);
  * the switch.  An rj_multi of ONE pattern takes the switch too.
  * Returns 1 when runs will take the one-kernel path, 0 when the set does not have the shape, < 0 rj_status. */
 int rj_multi_set_counts_only(rj_multi* multi, int on);
-/* rj_scan_set_timing for every pattern of the object (rj_multi_scan_ms reads 0 when off). */
+/* rj_scan_set_timing for every pattern of the object (rj_multi_scan_ms reads 0 when off).  On the one-kernel counts path the
+ * duration comes from the device's wall clock and switching it on puts nothing on the stream (see rj_scan_set_timing). */
 int rj_multi_set_timing(rj_multi* multi, int on);
 rj_scan* rj_multi_scan(rj_multi* multi, int i);
 /* First and last match of every pattern's result after rj_multi_run / _run_range: bounds[4*i .. 4*i+3] =

@@ -928,7 +928,8 @@ class MultiScan:
         return bool(_check(self._lib.rj_multi_set_counts_only(self._h, int(on))))
 
     def set_timing(self, on: bool = True) -> None:
-        """rj_multi_set_timing: without the scan kernel's start event scan_ms() reads 0 and consecutive kernels follow closer."""
+        """rj_multi_set_timing: without the scan kernel's start event scan_ms() reads 0 and consecutive kernels follow closer.
+        (The one-kernel counts path takes its duration from the device's wall clock: no event, nothing to gain by switching it off.)"""
         _check(self._lib.rj_multi_set_timing(self._h, int(on)))
 
     def order_after(self, other: Optional["MultiScan"]) -> None:

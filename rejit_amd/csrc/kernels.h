@@ -196,9 +196,12 @@ constexpr uint32_t kPcBounds = 0;                      // acc: [32][2] first / l
 constexpr uint32_t kPcTotals = kPcBounds + 64;         // [32]: the last run's counts (device copy)
 constexpr uint32_t kPcFinishGroups = 8;                // workgroups of plane_count_finish
 constexpr uint32_t kPcTicket = kPcTotals + 32;         // their ticket (zero between runs)
-constexpr uint32_t kPcGroupRows = kPcTicket + 16;      // [kPcFinishGroups][3][32]: their sums (slot 31: the flags) | first | last row + 1 with a match (0: none)
-constexpr uint32_t kPcAccWords = kPcGroupRows + kPcFinishGroups * 96;
-constexpr uint32_t kPcHostCount = 0, kPcHostFlags = 32, kPcHostBounds = 40, kPcHostWords = 40 + 64;
+constexpr uint32_t kPcGroupRows = kPcTicket + 16;      // [kPcFinishGroups][kPcGroupWords]: [3][32] their sums (slot 31: the flags) | first | last row + 1 with a match
+                                                       // (0: none), and behind them the earliest entry / latest exit stamp of their rows' workgroups (wg_clock)
+constexpr uint32_t kPcGroupClock = 96, kPcGroupWords = 98;
+constexpr uint32_t kPcAccWords = kPcGroupRows + kPcFinishGroups * kPcGroupWords;
+// host_out: counts [32], flags, bounds [32][2], and the scan's first entry / last exit by the device's wall clock (ticks)
+constexpr uint32_t kPcHostCount = 0, kPcHostFlags = 32, kPcHostBounds = 40, kPcHostClock = 40 + 64, kPcHostWords = kPcHostClock + 2;
 constexpr unsigned long long kPcNone = ~0ull;          // bounds: no match
 constexpr uint32_t kPcLenShift = 56;                   // a bound = begin | length << 56
 struct PlaneCountParams {
@@ -217,6 +220,7 @@ struct PlaneCountParams {
   unsigned long long* acc;
   uint32_t* wg_rows;                 // [grid][32]: every workgroup's counts (slot 31: its flags)
   unsigned long long* wg_bounds;     // [grid][32][2]: every workgroup's first / last match per pattern (as kPcBounds)
+  unsigned long long* wg_clock;      // [grid][2]: the device's wall clock (wall_clock64) at every workgroup's entry and at its exit (16-byte aligned)
   unsigned long long* host_out;
 };
 void launch_plane_count(const PlaneCountParams& a, int grid, hipEvent_t t0, hipEvent_t t1, hipStream_t st);

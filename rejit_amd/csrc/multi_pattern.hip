@@ -350,9 +350,12 @@ struct rj_multi {
   // rj_multi_set_counts_only: MatchAllCount in ONE kernel (plane_count.hip) for the sets exact_count.h takes
   bool counts_only = false;
   ExactCountPlan exact;
-  DeviceBuffer exact_table, count_acc, wg_rows, wg_bounds;
-  unsigned long long* count_out = nullptr;   // pinned: counts, flags, first / last match per pattern
+  DeviceBuffer exact_table, count_acc, wg_rows, wg_bounds, wg_clock;
+  unsigned long long* count_out = nullptr;   // pinned: counts, flags, first / last match per pattern, the scan's first entry / last exit (ticks)
   bool counts_ready = false;   // the buffers above are allocated and cleared
+  // the counts kernel's duration comes from the device's wall clock (plane_count.hip: wg_clock), not from a start event:
+  int clock_khz = -1;          // hipDeviceAttributeWallClockRate of the device of the first counts run (-1: not asked yet; 0: none -- the start event stays)
+  bool count_clocked = false;  // the run enqueued last left no start event on the stream
   // ... and for the sets the GENERAL plan takes (plane_count.hip: GeneralShape): the plan (== plane when that is the general
   // one), whether every pattern can be classified inside the kernel, the blob of descriptors + tables
   PlanePlan gplane;
@@ -1047,6 +1050,21 @@ bool counts_path(const rj_multi* m) {
 // rows (on ts, as enqueue_batched), collect_counts reads the result once it is in.  A void run (flags) is repeated by the span pipeline,
 // synchronously -- THAT run: the next one tries the kernel again (round 5 left the object on the span pipeline for good
 // after one tandem repeat).
+// scan_ms of such a run: the kernel's workgroups stamp their entry and exit with the device's constant-rate wall clock and
+// plane_count_finish hands the first entry and the last exit to the host with the counts -- no start event (a marker that drains
+// the queue for a host-side timestamp: ~6.5 us between two kernels of a stream) is put on the caller's stream.
+int count_clock_khz(rj_multi* m) {
+  if (m->clock_khz < 0) {
+    int dev = 0, khz = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      khz = 0;
+    }
+    m->clock_khz = khz > 0 ? khz : 0;
+  }
+  return m->clock_khz;
+}
+
 int enqueue_counts(rj_multi* m, MultiRun& r, hipStream_t ts) {
   rj_scan* const s0 = m->scans[0];
   hipStream_t st = r.st;
@@ -1096,12 +1114,17 @@ int enqueue_counts(rj_multi* m, MultiRun& r, hipStream_t ts) {
   pc.host_out = m->count_out;
   RJ_HIP(m->wg_rows.reserve(sizeof(uint32_t) * kExactMaxPatterns * static_cast<size_t>(geo.grid)));
   RJ_HIP(m->wg_bounds.reserve(sizeof(unsigned long long) * 2 * kExactMaxPatterns * static_cast<size_t>(geo.grid)));
+  RJ_HIP(m->wg_clock.reserve(sizeof(unsigned long long) * 2 * static_cast<size_t>(geo.grid)));
   pc.wg_rows = m->wg_rows.as<uint32_t>();
   pc.wg_bounds = m->wg_bounds.as<unsigned long long>();
+  pc.wg_clock = m->wg_clock.as<unsigned long long>();
   int rc = wait_scan_after(m, st);
   if (rc != RJ_OK) return rc;
-  if (general) launch_plane_count_general(pg, m->max_words, m->max_short, geo.grid, s0->t0(), s0->ev[2], st);
-  else launch_plane_count(pc, geo.grid, s0->t0(), s0->ev[2], st);
+  static const bool start_event = getenv("RJ_COUNT_START_EVENT") != nullptr;   // measurement override: the event-based scan_ms, for A/B runs
+  m->count_clocked = !start_event && count_clock_khz(m) > 0;
+  hipEvent_t t0 = m->count_clocked ? nullptr : s0->t0();   // (ev[2] stays: the tail stream waits for it)
+  if (general) launch_plane_count_general(pg, m->max_words, m->max_short, geo.grid, t0, s0->ev[2], st);
+  else launch_plane_count(pc, geo.grid, t0, s0->ev[2], st);
   // the rows added up: behind the scan, on the object's own stream when the caller keeps runs in flight (rj_multi_start):
   // the caller's stream is free for the next scan kernel at once
   if (ts != st) RJ_HIP(hipStreamWaitEvent(ts, s0->ev[2], 0));
@@ -1116,7 +1139,13 @@ int collect_counts(rj_multi* m, MultiRun& r) {
     int kind = run_spans(m, r);
     return kind < 0 ? kind : RJ_OK;
   }
-  read_scan_ms(m);
+  if (m->count_clocked) {
+    // first entry to last exit, in ticks of the device's wall clock (100 MHz on gfx950: 10 ns)
+    const unsigned long long in = m->count_out[kPcHostClock], out = m->count_out[kPcHostClock + 1];
+    m->scan_ms = m->scans[0]->timing && out > in ? static_cast<float>(static_cast<double>(out - in) / static_cast<double>(m->clock_khz)) : 0.f;
+  } else {
+    read_scan_ms(m);
+  }
   for (size_t p = 0; p < m->scans.size(); p++) {
     rj_scan* s = m->scans[p];
     s->stats = rj_stats{};

@@ -731,6 +731,15 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
     load_block(blk(c + 1), lane_rel, rb);
     behind = *reinterpret_cast<const uint2*>(a.text + static_cast<uint64_t>(fast_end) * kBlock);   // (block fast_end lies inside the text)
   }
+  // The workgroup's entry by the device's wall clock (s_memrealtime: the constant-rate 100 MHz counter a profiler's dispatch
+  // timestamps come from): it leaves with the row, beside a second reading taken there, and the host has the scan's duration
+  // -- first entry to last exit -- without a start event on the stream (multi_pattern.hip: enqueue_counts).  A scalar read into
+  // two scalar registers that stay put across the loop; every wave takes it (no branch), wave 0's is used.
+  // (HERE, a few dozen instructions into the kernel and before the first wait, not on its first line: the read counts as a
+  // side effect, and a uniform load behind one is no longer known to be unclobbered -- `behind` above turned from a scalar
+  // load into a vector load that held two more VGPRs across the loop, 71 instead of 69 for ExactShape<2>)
+  uint64_t clock_in = 0;
+  if constexpr (!S::kList) clock_in = __builtin_amdgcn_s_memrealtime();
   // the table / the blob (all waves), before the first wait for text
   if (S::kList) {
     // (nothing to stage: the candidates are classified by the next kernel)
@@ -863,6 +872,8 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
   if (lane == 0) wave_flags[wid] = w.flags;
   __syncthreads();
   if (wid != 0 || lane >= kExactMaxPatterns) return;
+  // (all four waves are through their spans: the workgroup's exit.  One plain 16-byte store, like the row's)
+  if (lane == 0) *reinterpret_cast<ulonglong2*>(a.wg_clock + static_cast<uint64_t>(blockIdx.x) * 2) = ulonglong2{clock_in, __builtin_amdgcn_s_memrealtime()};
   uint32_t v = wave_counts[0][lane] + wave_counts[1][lane] + wave_counts[2][lane] + wave_counts[3][lane];
   if (lane == kExactMaxPatterns - 1) v = wave_flags[0] | wave_flags[1] | wave_flags[2] | wave_flags[3];   // (slot 31: the flags)
   a.wg_rows[static_cast<uint64_t>(blockIdx.x) * kExactMaxPatterns + lane] = v;
@@ -886,15 +897,18 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
 // patterns (t & 7) of its group's rows t >> 3, + 32, ... with up to 14 16-byte loads in flight and remembers the first /
 // last row with a count; the group's sums go to acc, a ticket (eight arrivals: the cost of an atomic with return does not
 // matter here) finds the last group, which adds them up and reads, in one more trip, the first match of every pattern's
-// first row with a count and the last match of its last one.
+// first row with a count and the last match of its last one.  The workgroups' clock stamps go the same way: every group's
+// earliest entry and latest exit behind its sums, the last group's minimum / maximum of those to the host (kPcHostClock).
 // (<= 64 VGPRs -- __launch_bounds__(256, 8), eight loads in flight instead of fourteen, the reduce loops not unrolled: a workgroup of this kernel starts under a
 // running scan as soon as ONE scan wave per SIMD has retired; with its 132 VGPRs of round 6's first version it waited for three)
 constexpr uint32_t kFinishBatch = 8;
 __global__ __launch_bounds__(256, 8) void plane_count_finish(PlaneCountParams a, uint32_t n_wg) {
   __shared__ unsigned long long part[32][kExactMaxPatterns];
   __shared__ uint32_t part_first[32][kExactMaxPatterns], part_last[32][kExactMaxPatterns];   // row + 1; 0: none
+  __shared__ unsigned long long part_clock[4][2];   // per wave: the earliest entry, the latest exit of its rows' workgroups
   __shared__ uint32_t is_last;
   const uint32_t p4 = threadIdx.x & 7u, q = threadIdx.x >> 3;
+  const uint32_t lane = threadIdx.x & 63u, wave_id = threadIdx.x >> 6;
   const uint32_t per = (n_wg + gridDim.x - 1) / gridDim.x;
   const uint32_t r_lo = blockIdx.x * per, r_hi = r_lo + per < n_wg ? r_lo + per : n_wg;
   uint32_t sum[4] = {0, 0, 0, 0};   // (a thread adds <= n_wg / 256 rows of <= 163 840 matches each: 32 bits)
@@ -929,8 +943,22 @@ __global__ __launch_bounds__(256, 8) void plane_count_finish(PlaneCountParams a,
     part_first[q][4 * p4 + i] = first_row[i];
     part_last[q][4 * p4 + i] = last_row[i];
   }
+  // The scan's duration (PlaneCountParams::wg_clock): the earliest entry and the latest exit of the group's rows, one 16-byte
+  // load per row -- thread t takes rows t, t + 256, ... -- handed to the wave's minimum / maximum in LDS at once (64-bit LDS
+  // atomics without return; a wave's LDS operations happen in order: lane 0's start values first).  A pass of its own behind
+  // the sums, one more trip to memory: inside the loop above the stamps' four registers per thread, in flight or kept, are four
+  // more than the 64 this kernel may have -- it spilled.
+  if (lane == 0) {
+    part_clock[wave_id][0] = ~0ull;
+    part_clock[wave_id][1] = 0;
+  }
+  const ulonglong2* clocks = reinterpret_cast<const ulonglong2*>(a.wg_clock);
+  for (uint32_t r = r_lo + threadIdx.x; r < r_hi; r += 256) {
+    const ulonglong2 ck = clocks[r];
+    (void)__hip_atomic_fetch_min(&part_clock[wave_id][0], ck.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    (void)__hip_atomic_fetch_max(&part_clock[wave_id][1], ck.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
   __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u, wave_id = threadIdx.x >> 6;
   if (wave_id == 0) {
     if (lane < kExactMaxPatterns) {
       unsigned long long t = 0;
@@ -942,13 +970,22 @@ __global__ __launch_bounds__(256, 8) void plane_count_finish(PlaneCountParams a,
         f = pf != 0 && (f == 0 || pf < f) ? pf : f;
         l = pl > l ? pl : l;
       }
-      unsigned long long* g = a.acc + kPcGroupRows + blockIdx.x * 96;
+      unsigned long long* g = a.acc + kPcGroupRows + blockIdx.x * kPcGroupWords;
       __hip_atomic_store(&g[lane], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&g[32 + lane], static_cast<unsigned long long>(f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&g[64 + lane], static_cast<unsigned long long>(l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // (eight arrivals per launch: a release / acquire ticket costs nothing measurable here -- it is what the memory model asks for)
     if (lane == 0) {
+      unsigned long long in = part_clock[0][0], out = part_clock[0][1];
+#pragma unroll
+      for (int i = 1; i < 4; i++) {
+        in = part_clock[i][0] < in ? part_clock[i][0] : in;
+        out = part_clock[i][1] > out ? part_clock[i][1] : out;
+      }
+      unsigned long long* g = a.acc + kPcGroupRows + blockIdx.x * kPcGroupWords + kPcGroupClock;
+      __hip_atomic_store(&g[0], in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&g[1], out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const unsigned long long t = __hip_atomic_fetch_add(&a.acc[kPcTicket], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
       is_last = t + 1 == gridDim.x ? 1u : 0u;
       if (t + 1 == gridDim.x) __hip_atomic_store(&a.acc[kPcTicket], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (for the next run: exactly gridDim.x arrivals per launch)
@@ -960,9 +997,14 @@ __global__ __launch_bounds__(256, 8) void plane_count_finish(PlaneCountParams a,
   const uint32_t p = threadIdx.x;
   unsigned long long total = 0;
   uint32_t f = 0, l = 0;
+  unsigned long long in = ~0ull, out = 0;   // (every thread reads the groups' stamps -- one address per load --, thread 31 hands them on)
 #pragma unroll 2
   for (uint32_t g = 0; g < gridDim.x; g++) {
-    const unsigned long long* row = a.acc + kPcGroupRows + g * 96;
+    const unsigned long long* row = a.acc + kPcGroupRows + g * kPcGroupWords;
+    const unsigned long long gi = __hip_atomic_load(&row[kPcGroupClock], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long go = __hip_atomic_load(&row[kPcGroupClock + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    in = gi < in ? gi : in;
+    out = go > out ? go : out;
     const unsigned long long v = __hip_atomic_load(&row[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t pf = static_cast<uint32_t>(__hip_atomic_load(&row[32 + p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     const uint32_t pl = static_cast<uint32_t>(__hip_atomic_load(&row[64 + p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -970,7 +1012,11 @@ __global__ __launch_bounds__(256, 8) void plane_count_finish(PlaneCountParams a,
     f = pf != 0 && (f == 0 || pf < f) ? pf : f;
     l = pl > l ? pl : l;
   }
-  if (p == kExactMaxPatterns - 1) a.host_out[kPcHostFlags] = total;
+  if (p == kExactMaxPatterns - 1) {
+    a.host_out[kPcHostFlags] = total;
+    a.host_out[kPcHostClock] = in;
+    a.host_out[kPcHostClock + 1] = out;
+  }
   if (p >= a.n_patterns) return;
   unsigned long long first = kPcNone, last = kPcNone;
   if (total != 0 && f != 0) {   // (the scan kernel's plain stores: complete before this kernel began)
