@@ -380,6 +380,50 @@ typedef struct {
 int64_t rj_scan_records_sort(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
                              const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
                              uint64_t* d_order, rj_sort_stats* stats /* may be NULL */, void* hip_stream);
+/* The rows of one record table LOOKED UP IN ANOTHER (rejit_amd/csrc/record_lookup.hip): `grep -F -x -f
+ * KEYS`, `awk 'NR==FNR{s[$0];next} $3 in s'`, `comm`, Arrow's is_in / index_in, a semi-, anti- or inner join on a string key,
+ * a new batch encoded against an existing dictionary -- exactly (lengths and bytes are compared; a hash only finds the
+ * candidates), without a download.  Two record tables, the SET table over d_set_text[0, set_n) and the PROBE table over
+ * d_text[0, n), each with the row rules of rj_scan_records_pack / rj_scan_records_group: any order, repeats allowed through the
+ * index list, a non-NULL index list with count 0 is no rows.  The two texts may be the same buffer, overlap, or be unrelated.
+ * ks is the number of set rows, kp of probe rows; set row i is set_text[set_begin[rs(i)], set_end[rs(i)]), probe row j is
+ * text[rec_begin[r(j)], rec_end[r(j)]); a row's identity is its position i or j, not its record.  Two rows are equal when
+ * their lengths and bytes are; empty rows are equal to each other; "ab" and "ab\0" are different.
+ *     d_index[j]    = the smallest i whose set row equals probe row j, or RJ_LOOKUP_NONE     (kp uint64; index_in, first occurrence)
+ *     d_set_hits[i] = when i is the smallest set row with its string, the number of probe rows j with d_index[j] == i; for a
+ *                     later duplicate 0.  The hits add up to n_found                          (ks uint64, may be NULL)
+ * The answer is unique and depends on the rows alone.  The set rows whose d_set_hits is 0 at a first occurrence are the
+ * anti-join's right side (`comm -13`).  Returns n_found, the number of probe rows whose string is in the set.  Every row of
+ * d_index, and of d_set_hits when given, is written exactly once, nothing has to be cleared first, nothing behind kp or ks is
+ * touched.  ks == 0: every index is RJ_LOOKUP_NONE and the call returns 0.  kp == 0: returns 0, and d_set_hits, when given,
+ * is still written (all zero).  `stats` (may be NULL) receives what the call found.
+ * Composition: a lookup against the group call's dictionary -- the set rows d_rep of rj_scan_records_group over the set table,
+ * passed as d_set_indices (composed with that call's d_indices when there were any) -- gives every probe row its GROUP NUMBER
+ * directly: a new batch encoded against an existing dictionary, and the key step of an inner join (records.join_rows).
+ * The scan lends scratch only (the group call's 44 to 68 bytes per set row, 4 bytes per slot of hit counts, 8 bytes per probe
+ * row): spans, stats and the state of its last rj_scan_records (rj_scan_records_select included) stay as they were.  One
+ * synchronise per call.  Without d_set_hits and stats (is_in) the probes issue no atomic on the table or the counts.
+ * Refusals (RJ_BAD_ARGUMENT; a refused call writes no output row and is never led outside a text or a table): an index at or
+ * beyond its table's record count; a row without begin <= end <= its text's length -- the message names the table and the
+ * first bad row, "set row <i> " for the set, which is checked first, "row <j> " for the probe --; a null argument (per side:
+ * the text with a length > 0, the tables with a record count > 0; d_index with kp > 0); a table that is not 8-byte aligned.
+ * An output that overlaps an input is undefined, as elsewhere in the family.
+ * ks >= 2^31 or kp >= 2^31: RJ_TOO_LARGE (hit counts and the long list are 32-bit words in the scratch).
+ * The group call's knobs are read at every call: RJ_GROUP_HASH_BITS, RJ_GROUP_LONG_BYTES (both sides), RJ_GROUP_PEEL=0 (the
+ * set's inserts and the probes' hit counts each issue their own atomics).  No knobs of its own. */
+#define RJ_LOOKUP_NONE (~0ull)
+typedef struct {
+  uint64_t n_found;        /* probe rows whose string is in the set                        */
+  uint64_t n_set_distinct; /* distinct strings among the set rows (the group call's G)     */
+  uint64_t n_set_hit;      /* of those, strings that at least one probe row has            */
+  uint64_t long_rows;      /* probe rows handed to the wave tier                           */
+} rj_lookup_stats;
+int64_t rj_scan_records_lookup(rj_scan* scan, const void* d_set_text, uint64_t set_n, const uint64_t* d_set_begin,
+                               const uint64_t* d_set_end, uint64_t n_set_records, const uint64_t* d_set_indices,
+                               uint64_t n_set_indices, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                               const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
+                               uint64_t* d_index, uint64_t* d_set_hits /* may be NULL */,
+                               rj_lookup_stats* stats /* may be NULL */, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

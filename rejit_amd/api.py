@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_split.h", "record_group.h", "record_sort.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -165,6 +165,10 @@ class _SortStats(ctypes.Structure):
     _fields_ = [("rounds", ctypes.c_uint64), ("keyed_rows", ctypes.c_uint64), ("skip_rows", ctypes.c_uint64), ("long_rows", ctypes.c_uint64)]
 
 
+class _LookupStats(ctypes.Structure):
+    _fields_ = [("n_found", ctypes.c_uint64), ("n_set_distinct", ctypes.c_uint64), ("n_set_hit", ctypes.c_uint64), ("long_rows", ctypes.c_uint64)]
+
+
 class RecordsResult:
     """What Scan.run_records returns: rj_record_stats (n_kept, n_matching, n_crossing, n_matches) and the per-record tensors --
     counts (int32: the library's uint32, saturating, so 2^32 - 1 reads -1) and first (int64), both on the text's device.
@@ -199,7 +203,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup"]
 
 
 def load_library():
@@ -311,6 +315,8 @@ def load_library():
     L.rj_scan_records_group.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp]
     L.rj_scan_records_sort.restype = i64
     L.rj_scan_records_sort.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, ctypes.POINTER(_SortStats), vp]
+    L.rj_scan_records_lookup.restype = i64
+    L.rj_scan_records_lookup.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, vp, ctypes.POINTER(_LookupStats), vp]
     _lib = L
     return L
 
@@ -831,6 +837,51 @@ class Scan:
         if stats:
             return order, {f: int(getattr(out, f)) for f, _ in _SortStats._fields_}
         return order
+
+    def lookup_records(self, set_text, set_begin, set_end, text, rec_begin, rec_end, set_indices=None, indices=None, hits=False, stats=False, stream=None):
+        """rj_scan_records_lookup: the probe rows text[rec_begin[i], rec_end[i]) looked up in the set rows set_text[set_begin[i],
+        set_end[i]) -- on either side all rows, or those the side's index list names, as pack_records' -- by their bytes,
+        exactly: Arrow's index_in / is_in, `grep -F -x -f`, a semi-join.  The two texts may be one tensor, overlap or be
+        unrelated; they are on the same device.  Returns `index`, an int64 device tensor of kp entries: the smallest set row
+        equal to probe row j, or -1 (RJ_LOOKUP_NONE); index >= 0 is is_in.  With hits=True also `hits` (int64, ks entries):
+        at the smallest set row of a string the number of probe rows that found it, 0 at a later duplicate -- 0 at a first
+        occurrence is the anti-join's right side.  With stats=True also {"n_found", "n_set_distinct", "n_set_hit",
+        "long_rows"}.  With set_indices = the `rep` of group_records over the set table, index holds the probe rows' group
+        numbers (records.join_rows makes the inner join of them).  RejitError (RJ_BAD_ARGUMENT, naming the table and the first
+        bad row: "set row <i> " / "row <j> ") for a bad index or row.  The scan's spans, stats and select_records stay as
+        they were."""
+        import torch
+
+        t = text
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        assert set_text.dtype == torch.uint8 and set_text.is_contiguous() and set_text.device == t.device
+        n_set_records, n_records = int(set_begin.numel()), int(rec_begin.numel())
+        for x, count in ((set_begin, n_set_records), (set_end, n_set_records), (rec_begin, n_records), (rec_end, n_records)):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == count
+
+        def rows(idx, every):
+            if idx is None:
+                return None, every
+            assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.device == t.device
+            if idx.numel() == 0:
+                return torch.zeros(1, dtype=torch.int64, device=t.device), 0   # (a non-null pointer: NULL means every record)
+            return idx, int(idx.numel())
+        set_indices, ks = rows(set_indices, n_set_records)
+        indices, kp = rows(indices, n_records)
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        index = torch.empty(kp, dtype=torch.int64, device=t.device)
+        set_hits = torch.empty(ks, dtype=torch.int64, device=t.device) if hits else None
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        out = _LookupStats()
+        _check(self._lib.rj_scan_records_lookup(self._h, ptr(set_text), int(set_text.numel()), ptr(set_begin), ptr(set_end), n_set_records, ptr(set_indices), ks,
+                                                ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), kp, ptr(index), ptr(set_hits),
+                                                ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
+        answer = (index,)
+        if hits:
+            answer += (set_hits,)
+        if stats:
+            answer += ({f: int(getattr(out, f)) for f, _ in _LookupStats._fields_},)
+        return answer if len(answer) > 1 else index
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""

@@ -124,3 +124,24 @@ def sorted_groups(scan, text, rec_begin, rec_end, indices=None):
     rank = torch.empty_like(order)
     rank[order] = torch.arange(order.numel(), dtype=torch.int64, device=order.device)
     return rep[order].contiguous(), count[order].contiguous(), rank[group].contiguous()
+
+
+def join_rows(index, set_group, set_count):
+    """(probe_row, set_row): ALL pairs of the inner join of a probe table with a set table on their rows' bytes, int64 tensors
+    of equal length on index's device.  index: Scan.lookup_records of the probe rows against the set's dictionary -- the rows
+    `rep` of Scan.group_records over the set table as set_indices --, so a group number per probe row, or -1; set_group and
+    set_count: that group call's `group` and `count`.  The pairs are ordered by probe row, then by ascending set row.  Torch
+    only and device-agnostic: a stable argsort of set_group lists every group's set rows in ascending order, an exclusive
+    cumsum of set_count says where a group's run begins, repeat_interleave expands every probe row by its group's count."""
+    import torch
+
+    found = torch.nonzero(index >= 0).reshape(-1)
+    groups = index[found]
+    by_group = torch.argsort(set_group, stable=True)
+    first = torch.cumsum(set_count, 0) - set_count
+    counts = set_count[groups]
+    probe_row = torch.repeat_interleave(found, counts)
+    begin = torch.cumsum(counts, 0) - counts                      # where a probe row's pairs begin in the output
+    within = torch.arange(probe_row.numel(), dtype=torch.int64, device=index.device) - torch.repeat_interleave(begin, counts)
+    set_row = by_group[torch.repeat_interleave(first[groups], counts) + within]
+    return probe_row.contiguous(), set_row.contiguous()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K]] [-b] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K]] [-b] [-k KEYS] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -26,6 +26,13 @@ answer on the GPU:
   -b   byte order (`LC_ALL=C sort`), made on the device by rj_scan_records_sort: with -u the distinct values print in the
        order of their bytes with their counts (`... | sort | uniq -c`; with -t K the K most frequent, ties in byte order);
        with -p, -o or -f N and no -u the selected lines, the matches or the fields print sorted (`... | sort`)
+  -k KEYS   select the lines that have a match of PATTERN AND are equal to a line of the file KEYS (`grep -E PATTERN FILE |
+       grep -F -x -f KEYS`); with -f N, where PATTERN is the separator, the lines whose field N is a line of KEYS (`awk -F
+       PATTERN 'NR==FNR{s[$0];next} $N in s' KEYS FILE`; a line with fewer fields is not selected).  -v inverts the whole
+       selection.  KEYS is uploaded as a second device text; its rows are its lines (without the last, empty one when it ends
+       in a line break, as `grep -f` reads it), and rj_scan_records_lookup looks the lines or the fields up in them on the
+       device: only the count (-c), the numbers (-n) or the packed lines (-p) come back.  Beside -k only -c, -n, -p, -v and
+       -f N are allowed.
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -50,12 +57,17 @@ def main(argv):
     if "-t" in argv[:-1]:
         at = argv.index("-t")
         top, argv = argv[at + 1], argv[:at] + argv[at + 2:]
+    keys = None
+    if "-k" in argv[:-1]:
+        at = argv.index("-k")
+        keys, argv = argv[at + 1], argv[:at] + argv[at + 2:]
     matches_out, unique, byte_order = "-o" in argv, "-u" in argv, "-b" in argv
     argv = [a for a in argv if a not in ("-o", "-u", "-b")]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
     if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)) or (top is not None and (not top.isdigit() or not unique)) or (
-            unique and not matches_out and field is None) or (byte_order and not matches_out and field is None and "-p" not in flags):
+            unique and not matches_out and field is None) or (byte_order and not matches_out and field is None and "-p" not in flags) or (
+            keys is not None and (repl is not None or top is not None or matches_out or unique or byte_order)):
         sys.stderr.write(__doc__)
         return 2
     path, pattern = rest
@@ -83,6 +95,39 @@ def main(argv):
     scan = rejit_amd.Scan(rejit_amd.Program(pattern))
     result = scan.run_records(text, begins, ends)
     selected = result.n_records - result.n_matching if invert else result.n_matching
+    if keys is not None:
+        key_data = np.fromfile(keys, dtype=np.uint8)
+        key_text = torch.from_numpy(key_data if key_data.size else np.zeros(1, dtype=np.uint8)).to("cuda:0")     # the second upload
+        if key_data.size:
+            kb, ke = records.line_records(key_text)
+            if key_data[-1] in (10, 13):                             # (the empty record behind the last line break is not a key)
+                kb, ke = kb[:-1].contiguous(), ke[:-1].contiguous()
+        else:
+            kb = ke = torch.empty(0, dtype=torch.int64, device="cuda:0")
+        if field is None:
+            rows, rb, re_ = scan.select_records(), begins, ends      # the lines with a match, looked up whole
+        else:
+            pb, pe, pf = scan.split_records(begins, ends, result, int(text.numel()), what="between")
+            rb, re_, present = records.field_records(pb, pe, pf, int(field) - 1)
+            rows = torch.nonzero(present).reshape(-1).contiguous()   # the lines that have a field N, looked up by it
+        index = scan.lookup_records(key_text, kb, ke, text, rb, re_, indices=rows)
+        lines = rows[index >= 0]
+        if invert:
+            keep = torch.ones(result.n_records, dtype=torch.bool, device="cuda:0")
+            keep[lines] = False
+            lines = torch.nonzero(keep).reshape(-1)
+        lines = lines.contiguous()
+        selected = int(lines.numel())
+        if numbers:
+            sys.stdout.write("".join("%d\n" % (i + 1) for i in lines.cpu().tolist()))
+        elif lines_out:
+            if selected:
+                packed, _, _ = scan.pack_records(text, begins, ends, indices=lines, fill=10, lead=0, gap=1)
+                sys.stdout.flush()
+                sys.stdout.buffer.write(packed.cpu().numpy().tobytes())
+        else:
+            print(selected)
+        return 0 if selected else 1
     if repl is not None:
         every = not invert and "-p" not in flags
         lines = None if every else scan.select_records(invert=invert)
