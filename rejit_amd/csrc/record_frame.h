@@ -1,12 +1,16 @@
-// rejit_amd/csrc/record_frame.h -- what the record units (record_join.hip, record_pack.hip, record_replace.hip) share, in ONE
-// place: the summary words of their calls, the 64-bit wave sums, the 16-byte read of a device text at any alignment, the unit
-// of a persistent scan in arrival order (ticket, publish, resolve, timed-out), the plan over it, the output-major chunk copy,
-// and the host plumbing around the launches.  Everything lives in an anonymous namespace: every unit gets its own copy.
+// rejit_amd/csrc/record_frame.h -- what the record units (record_join.hip, record_pack.hip, record_replace.hip,
+// record_split.hip, record_group.hip with record_group_build.h, record_sort.hip, record_lookup.hip) share, in ONE place: the
+// summary words of their calls and when they refuse one, the 64-bit wave sums, the first bad row and the list of flagged
+// rows as a wave leaves them, the 16-byte read of a device text at any alignment (record_rows.h's Text), the rows of a
+// record table, the unit of a persistent scan in arrival order (ticket, publish, resolve, timed-out), the plan over it, the
+// output-major chunk copy, and the host plumbing around the launches.  Everything lives in an anonymous namespace: every
+// unit gets its own copy.
 #ifndef REJIT_AMD_RECORD_FRAME_H_
 #define REJIT_AMD_RECORD_FRAME_H_
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "engine_internal.h"
 #include "kernel_util.h"
@@ -29,6 +33,9 @@ constexpr unsigned kCopyGrid = 256 * 8;   // persistent: eight workgroups for ea
 // first row: ~row (join, pack), replace::bad_word (replace).
 enum { kSumKept = 0, kSumMatching, kSumCrossing, kSumBadWord, kSumSelected, kSumTotal, kSumTimedOut, kSumWords = 8 };
 
+// a refused call: a bad row, or a unit scan that timed out -- its tables are not followed anywhere, and no output row is written
+__device__ __forceinline__ bool refused(const unsigned long long* summary) { return summary[kSumBadWord] != 0 || summary[kSumTimedOut] != 0; }
+
 // ---------------------------------------------------------------------------------------------------------------- wave sums
 // 64-bit sum / inclusive prefix sum over the wave from wave_ops.h's 32-bit ones: three pieces of at most 22 bits (64 x 2^22 fits)
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
@@ -44,12 +51,36 @@ __device__ __forceinline__ uint64_t wave_inclusive_sum64(uint64_t x) {
   return a + (b << 22) + (c << 44);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- wave lists
+// The first bad row wins: the lowest lane of the wave that has a bad row gives its row's word to *bad_word by ONE atomic max
+// -- a wave's rows ascend with its lanes, and every encoding makes the first row the largest word.
+__device__ __forceinline__ void note_bad_word(bool bad, unsigned long long word, unsigned long long* bad_word) {
+  const uint64_t bad_lanes = __ballot(bad);
+  if (bad_lanes && lane_id() == __builtin_ctzll(bad_lanes)) atomicMax(bad_word, word);
+}
+// ... row j in the encoding ~j
+__device__ __forceinline__ void note_bad_row(bool bad, uint64_t j, unsigned long long* bad_word) {
+  note_bad_word(bad, static_cast<unsigned long long>(~j), bad_word);
+}
+// The flagged lanes' values appended to list[*counter ...): one ballot, ONE atomic add per wave (the leader's, of the
+// popcount), the base broadcast, every flagged lane stores at base + the flagged lanes below it.
+__device__ __forceinline__ void wave_append(bool flag, uint32_t value, unsigned long long* counter, uint32_t* list) {
+  const uint64_t lanes = __ballot(flag);
+  if (!lanes) return;
+  const int leader = __builtin_ctzll(lanes);
+  unsigned long long base = 0;
+  if (lane_id() == leader) base = atomicAdd(counter, static_cast<unsigned long long>(__popcll(lanes)));
+  base = lane_value(base, leader);
+  if (flag) list[base + lanes_below(lanes)] = value;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- text
 // text[s, s + 16), all of it inside [0, n): two aligned 16-byte loads around it and a funnel shift by the source's
 // misalignment, or ONE load when source and destination are aligned alike.  That one is a streaming read (stream_load.h:
 // every cache line is asked for by one instruction); the two loads of the misaligned case ask for a line twice -- a lane's
 // second block is its neighbour's first -- and keep the default policy.  At the text's two ends, where an aligned block
-// would reach outside [0, n), kernel_util.h's guarded load reads the 16 bytes one by one.
+// would reach outside [0, n), kernel_util.h's guarded load reads the 16 bytes one by one.  load16_guarded is that load for
+// any s: with it DeviceText is record_rows.h's Text.
 struct DeviceText {
   const uint8_t* text;
   uint64_t n;
@@ -79,7 +110,20 @@ struct DeviceText {
 #pragma unroll
     for (int i = 0; i < 4; i++) w[i] = __builtin_amdgcn_alignbyte(y[i + 1], y[i], bs);
   }
+  __device__ __forceinline__ void load16_guarded(uint64_t s, uint32_t w[4]) const {
+    uint32_t d[6];
+    load_guarded(text, n, s, d);
+    w[0] = d[0], w[1] = d[1], w[2] = d[2], w[3] = d[3];
+  }
   __device__ __forceinline__ uint32_t byte(uint64_t s) const { return s < n ? text[s] : 0u; }
+};
+
+// the rows of a call: row j is record indices[j], or record j
+struct Rows {
+  const uint64_t* __restrict__ rec_begin;
+  const uint64_t* __restrict__ rec_end;
+  const uint64_t* __restrict__ indices;
+  __device__ __forceinline__ uint64_t record(uint64_t j) const { return indices ? indices[j] : j; }
 };
 
 // ---------------------------------------------------------------------------------------------------------------- unit scan
@@ -179,8 +223,7 @@ __device__ __forceinline__ void plan_units(const RowFn& row, uint64_t k, uint64_
     PlannedRow r{0, 0};
     if (j < k) r = row(j);
     const uint64_t add = j < k ? pack::row_advance(r.bad != 0, 0, r.len, gap) : 0;
-    const uint64_t bad_lanes = __ballot(r.bad != 0);
-    if (bad_lanes && lane_id() == __builtin_ctzll(bad_lanes)) atomicMax(&summary[kSumBadWord], r.bad);
+    note_bad_word(r.bad != 0, r.bad, &summary[kSumBadWord]);
     uint64_t before, unit_end;
     const bool ok = unit_exclusive_sum(s_unit, add, tk, n_units, granules, summary, &before, &unit_end);
     if (ok && tk == n_units - 1 && tid == 0) summary[kSumTotal] = lead + unit_end;
@@ -207,7 +250,7 @@ __device__ __forceinline__ void copy_chunks(const Policy& P, const uint8_t* __re
                                             uint64_t out_cap, const unsigned long long* summary) {
   __shared__ typename Policy::Stage s_stage;
   __shared__ uint64_t s_rows[2];
-  if (summary[kSumBadWord] != 0 || summary[kSumTimedOut] != 0) return;   // a refused plan: its tables are not followed anywhere
+  if (refused(summary)) return;
   const uint64_t total = summary[kSumTotal];
   const uint64_t limit = total < out_cap ? total : out_cap;
   const uint64_t n_chunks = (limit + chunk - 1) / chunk;
@@ -279,6 +322,16 @@ inline int records_finish(rj_scan* s, const char* call, hipStream_t st) {
   RJ_HIP(hipGetLastError());
   if (s->rec_host[kSumTimedOut] != 0) return rj_fail(RJ_DEVICE_ERROR, "%s: the look-back timed out", call);
   return RJ_OK;
+}
+
+// a test knob of a call, read at every call: the number in the environment's `name`, at most `most`; `otherwise` without one
+inline uint32_t env_number(const char* name, uint32_t otherwise, uint32_t most) {
+  const char* v = getenv(name);
+  if (!v || !*v) return otherwise;
+  char* end = nullptr;
+  const unsigned long long x = strtoull(v, &end, 10);
+  if (!end || *end) return otherwise;
+  return x > most ? most : static_cast<uint32_t>(x);
 }
 
 // the argument checks rj_scan_records_pack and rj_scan_records_replace share (each checks its own tables' alignment behind them)

@@ -1,7 +1,8 @@
 // rejit_amd/csrc/record_group.h -- the arithmetic of rj_scan_records_group (record_group.hip): the rows of a record table grouped
 // by their BYTES -- Arrow's dictionary_encode / value_counts, `sort | uniq -c` in order of first appearance -- exactly, with no
 // probabilistic equality.  Host and device code: the CPU tests drive exactly these functions (tests/support/group_exec.cc)
-// through a Text and a Mem policy, as the kernels do.
+// through a Text and a Mem policy, as the kernels do.  What a row's bytes are -- the limits, the guarded 16-byte groups, their
+// equality, the Text policy -- is record_rows.h's.
 //
 // Row j is text[rb, re) of record r(j).  Its key:
 //     hash(row) = finalize(len, sum over g of mix(words of 16-byte group g, g))       (the sum mod 2^64)
@@ -32,20 +33,21 @@
 #include <stdint.h>
 
 #include "record_pack.h"
+#include "record_rows.h"
 
 namespace rejit_amd {
 namespace group {
 
 constexpr uint64_t kEmpty = ~0ull;
-constexpr uint64_t kGroupBytes = 16;
-constexpr uint64_t kMaxRows = 1ull << 31;        // rows and slots share 32-bit words in the scratch (slot_of, slot_group, counts)
 constexpr uint64_t kMinSlots = 64;
-constexpr uint32_t kLongBytes = 64;              // rows longer than this are walked by a wave, not a lane
-constexpr uint32_t kMaxLongBytes = 1u << 20;     // the most the lane tier may be asked to take (RJ_GROUP_LONG_BYTES)
+constexpr uint32_t kLongBytes = 64;              // rows longer than this are walked by a wave, not a lane (RJ_GROUP_LONG_BYTES)
 constexpr uint32_t kLenSaturated = 0xFFFFFFFFu;  // the stored length of a row of 2^32 - 1 bytes or more: its table has the length
 
 // ---------------------------------------------------------------------------------------------------------------- limits
-RJ_PACK_HD inline bool rows_fit(uint64_t k) { return k < kMaxRows; }
+// A call takes rows_fit(k) rows: rows and slots share 32-bit words in the scratch (slot_of, slot_group, counts).  (record_rows.h's
+// rows_fit and n_groups under this header's names: one definition, the names its callers have always used.)
+using rows::n_groups;
+using rows::rows_fit;
 // max(64, the next power of two >= 2k); k < 2^31, so at most 2^32 slots and a slot's index fits 32 bits
 RJ_PACK_HD inline uint64_t table_slots(uint64_t k) {
   uint64_t t = kMinSlots;
@@ -58,8 +60,8 @@ RJ_PACK_HD inline uint64_t table_slots(uint64_t k) {
 struct Layout {
   uint64_t table, slot_count, slot_group, hash, len, slot_of, long_list, bytes;
 };
-RJ_PACK_HD inline uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
 RJ_PACK_HD inline Layout layout(uint64_t k) {
+  using rows::align16;
   const uint64_t T = table_slots(k);
   Layout l;
   l.table = 0;
@@ -75,8 +77,6 @@ RJ_PACK_HD inline Layout layout(uint64_t k) {
 RJ_PACK_HD inline uint32_t stored_len(uint64_t len) { return len >= kLenSaturated ? kLenSaturated : static_cast<uint32_t>(len); }
 
 // ---------------------------------------------------------------------------------------------------------------- hash
-RJ_PACK_HD inline uint64_t n_groups(uint64_t len) { return (len + kGroupBytes - 1) / kGroupBytes; }
-
 // multiply / xor-shift over the four little-endian words of group g
 RJ_PACK_HD inline uint64_t mix(const uint32_t w[4], uint64_t g) {
   const uint64_t a = static_cast<uint64_t>(w[0]) | (static_cast<uint64_t>(w[1]) << 32);
@@ -99,58 +99,32 @@ RJ_PACK_HD inline uint64_t finalize(uint64_t len, uint64_t sum) {
 // RJ_GROUP_HASH_BITS: only the low `bits` bits of every hash are kept (and stored: the equality check sees the same value)
 RJ_PACK_HD inline uint64_t keep_bits(uint64_t h, uint32_t bits) { return bits >= 64 ? h : h & ((1ull << bits) - 1); }
 
-// the bytes at and beyond `valid` (1..16) of a group become zero
-RJ_PACK_HD inline void mask_group(uint32_t w[4], uint32_t valid) {
-  for (uint32_t i = 0; i < 4; i++) {
-    const uint32_t lo = 4 * i;
-    if (valid <= lo) w[i] = 0;
-    else if (valid < lo + 4) w[i] &= (1u << (8 * (valid - lo))) - 1;
-  }
-}
-
-// Group g (< n_groups(len)) of the row [begin, begin + len) of a text of n bytes, zero-padded beyond the row's end.  Text:
-// load16(s, w) reads text[s, s + 16), all of it inside [0, n); load16_guarded(s, w) reads the bytes below n one by one and
-// zeroes behind them -- taken where 16 bytes would reach outside the text.
-template <class Text>
-RJ_PACK_HD inline void load_group(const Text& text, uint64_t n, uint64_t begin, uint64_t len, uint64_t g, uint32_t w[4]) {
-  const uint64_t s = begin + g * kGroupBytes;
-  const uint64_t left = len - g * kGroupBytes;
-  if (s + kGroupBytes <= n) text.load16(s, w);
-  else text.load16_guarded(s, w);
-  if (left < kGroupBytes) mask_group(w, static_cast<uint32_t>(left));
-}
-
 // the sum of mix over the groups g0, g0 + stride, ... below g_end: a lane's, a wave iteration's or the whole row's share
 template <class Text>
 RJ_PACK_HD inline uint64_t hash_groups(const Text& text, uint64_t n, uint64_t begin, uint64_t len, uint64_t g0, uint64_t stride, uint64_t g_end) {
   uint64_t sum = 0;
   for (uint64_t g = g0; g < g_end; g += stride) {
     uint32_t w[4];
-    load_group(text, n, begin, len, g, w);
+    rows::load_group(text, n, begin, len, g, w);
     sum += mix(w, g);
   }
   return sum;
 }
 template <class Text>
 RJ_PACK_HD inline uint64_t hash_row(const Text& text, uint64_t n, uint64_t begin, uint64_t len) {
-  return finalize(len, hash_groups(text, n, begin, len, 0, 1, n_groups(len)));
+  return finalize(len, hash_groups(text, n, begin, len, 0, 1, rows::n_groups(len)));
 }
 
-// group g of two rows of the same length: equal?
+// group g of two rows of ONE text, of the same length: equal?  (rows::group_equal with both sides in the same text)
 template <class Text>
 RJ_PACK_HD inline bool group_equal(const Text& text, uint64_t n, uint64_t a, uint64_t b, uint64_t len, uint64_t g) {
-  uint32_t x[4], y[4];
-  load_group(text, n, a, len, g, x);
-  load_group(text, n, b, len, g, y);
-  return ((x[0] ^ y[0]) | (x[1] ^ y[1]) | (x[2] ^ y[2]) | (x[3] ^ y[3])) == 0;
+  return rows::group_equal(text, n, a, text, n, b, len, g);
 }
-// ... the groups g0, g0 + stride, ... below g_end (a lane walks a short row with g0 = 0, stride = 1)
+// ... the groups g0, g0 + stride, ... below g_end (a lane walks a short row with g0 = 0, stride = 1); a row is equal to itself
 template <class Text>
 RJ_PACK_HD inline bool groups_equal(const Text& text, uint64_t n, uint64_t a, uint64_t b, uint64_t len, uint64_t g0, uint64_t stride, uint64_t g_end) {
   if (a == b) return true;
-  for (uint64_t g = g0; g < g_end; g += stride)
-    if (!group_equal(text, n, a, b, len, g)) return false;
-  return true;
+  return rows::groups_equal(text, n, a, text, n, b, len, g0, stride, g_end);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- insert

@@ -16,7 +16,7 @@
 #include "record_frame.h"
 #include "record_group.h"
 #include "record_group_build.h"
-#include "record_pack.h"
+#include "record_rows.h"
 
 namespace rejit_amd {
 
@@ -27,6 +27,9 @@ __global__ __launch_bounds__(kThreads) void record_group_number_kernel(uint64_t 
                                                                        unsigned long long* ticket, uint64_t* __restrict__ rep,
                                                                        uint64_t* __restrict__ group_count, uint64_t group_cap, unsigned long long* summary) {
   __shared__ UnitSum s_unit;
+  // Only the bad word, not refused(): kSumTimedOut is written by this kernel's own unit scan and by nothing before it in the
+  // call, so it can be set here only by another workgroup of this launch -- and a workgroup that starts behind a time-out
+  // still takes its units and publishes them (nobody waits on words it left out); the call fails at its end either way.
   if (summary[kSumBadWord] != 0) return;
   LaneMem M{S};
   unit_init(s_unit.place);
@@ -79,7 +82,7 @@ int64_t rj_scan_records_group(rj_scan* s, const void* d_text, uint64_t n, const 
   if (!aligned8(d_rec_begin, d_rec_end, d_indices, d_group, d_rep, d_group_count))
     return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records_group: a table is not 8-byte aligned");
   const uint64_t k = d_indices ? n_indices : n_records;
-  if (!group::rows_fit(k))
+  if (!rows::rows_fit(k))
     return rj_fail(RJ_TOO_LARGE, "rj_scan_records_group: %llu rows: rows and slots share 32-bit words in the scratch (fewer than 2^31 rows)",
                    static_cast<unsigned long long>(k));
   if (k == 0) return 0;

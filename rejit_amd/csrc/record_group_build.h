@@ -2,8 +2,8 @@
 // need it: rj_scan_records_group (record_group.hip) numbers the table's strings, rj_scan_records_lookup (record_lookup.hip)
 // probes it with the rows of another table.  Two memsets and four launches on one stream (group_build):
 //
-// Hash (lane): one row per lane.  The pack's checks (the first bad row wins by one atomic max); rows of at most L bytes get
-//   their 64-bit key and a 32-bit length, longer ones are appended to a list (one ballot, one atomic add per wave).
+// Hash (lane): one row per lane.  The pack's checks (rows::resolve; the first bad row wins, note_bad_row); rows of at most L
+//   bytes get their 64-bit key and a 32-bit length, longer ones are appended to a list (wave_append).
 // Hash (wave): one wave per listed row, 64 lanes x 16 bytes = 1 KiB per iteration, the lanes' partial sums added by wave_sum64.
 // Insert (lane): one row per lane into the open-addressing table; the byte compare covers at most L bytes.  The lanes of a
 //   wave that ended at the slot of the wave's first active lane issue ONE atomic add and ONE atomic min (the peel: a column
@@ -11,39 +11,21 @@
 // Insert (wave): one wave per listed row; lane 0 does the atomics, the answers are broadcast; 1 KiB per compare iteration,
 //   a ballot ends it at the first difference.
 // Every kernel behind the first returns at once when the summary holds a bad row.  Nothing here waits for another lane's
-// progress (record_group.h).  Like record_frame.h everything lives in an anonymous namespace: every unit gets its own copy.
+// progress (record_group.h).  The rows, the text, the refusal, the two wave idioms and the knobs' parser are record_frame.h's;
+// like it everything here lives in an anonymous namespace: every unit gets its own copy.
 #ifndef REJIT_AMD_RECORD_GROUP_BUILD_H_
 #define REJIT_AMD_RECORD_GROUP_BUILD_H_
 
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include "engine_internal.h"
 #include "record_frame.h"
 #include "record_group.h"
-#include "record_pack.h"
+#include "record_rows.h"
 
 namespace rejit_amd {
 
 namespace {
-
-// record_group.h's Text over record_frame.h's DeviceText
-struct GroupText {
-  DeviceText t;
-  __device__ __forceinline__ void load16(uint64_t s, uint32_t w[4]) const { t.load16(s, w); }
-  __device__ __forceinline__ void load16_guarded(uint64_t s, uint32_t w[4]) const {
-    uint32_t d[6];
-    load_guarded(t.text, t.n, s, d);
-    w[0] = d[0], w[1] = d[1], w[2] = d[2], w[3] = d[3];
-  }
-};
-
-struct Rows {
-  const uint64_t* __restrict__ rec_begin;
-  const uint64_t* __restrict__ rec_end;
-  const uint64_t* __restrict__ indices;
-  __device__ __forceinline__ uint64_t record(uint64_t j) const { return indices ? indices[j] : j; }
-};
 
 // the scratch of a call (group::layout)
 struct Scratch {
@@ -58,48 +40,33 @@ struct Scratch {
   uint64_t T;
 };
 
-__device__ __forceinline__ bool refused(const unsigned long long* summary) { return summary[kSumBadWord] != 0 || summary[kSumTimedOut] != 0; }
-
 // ---------------------------------------------------------------------------------------------------------------- hash
 __global__ __launch_bounds__(kThreads) void record_group_hash_kernel(const uint8_t* __restrict__ text, uint64_t n, Rows R, uint64_t n_records, uint64_t k,
                                                                      uint64_t n_units, uint32_t long_bytes, uint32_t hash_bits, Scratch S,
                                                                      unsigned long long* summary) {
-  const GroupText src{DeviceText{text, n}};
+  const DeviceText src{text, n};
   for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
     const uint64_t j = unit * kThreads + threadIdx.x;
     bool bad = false, is_long = false;
     if (j < k) {
-      const uint64_t r = R.record(j);
-      bad = pack::bad_index(r, n_records);
-      uint64_t rb = 0, re = 0;
+      const rows::Row row = rows::resolve(R.rec_begin, R.rec_end, R.indices, n_records, n, j);
+      bad = row.bad;
       if (!bad) {
-        rb = R.rec_begin[r], re = R.rec_end[r];
-        bad = pack::bad_row(rb, re, n);
-      }
-      if (!bad) {
-        const uint64_t len = re - rb;
+        const uint64_t len = row.len();
         S.len[j] = group::stored_len(len);
         is_long = len > long_bytes;
-        if (!is_long) S.hash[j] = group::keep_bits(group::hash_row(src, n, rb, len), hash_bits);
+        if (!is_long) S.hash[j] = group::keep_bits(group::hash_row(src, n, row.rb, len), hash_bits);
       }
     }
-    const uint64_t bad_lanes = __ballot(bad);
-    if (bad_lanes && lane_id() == __builtin_ctzll(bad_lanes)) atomicMax(&summary[kSumBadWord], static_cast<unsigned long long>(~j));
-    const uint64_t long_lanes = __ballot(is_long);
-    if (long_lanes) {
-      const int leader = __builtin_ctzll(long_lanes);
-      unsigned long long base = 0;
-      if (lane_id() == leader) base = atomicAdd(S.long_count, static_cast<unsigned long long>(__popcll(long_lanes)));
-      base = lane_value(base, leader);
-      if (is_long) S.long_list[base + lanes_below(long_lanes)] = static_cast<uint32_t>(j);
-    }
+    note_bad_row(bad, j, &summary[kSumBadWord]);
+    wave_append(is_long, static_cast<uint32_t>(j), S.long_count, S.long_list);
   }
 }
 
 __global__ __launch_bounds__(kThreads) void record_group_hash_long_kernel(const uint8_t* __restrict__ text, uint64_t n, Rows R, uint32_t hash_bits, Scratch S,
                                                                           const unsigned long long* summary) {
   if (refused(summary)) return;
-  const GroupText src{DeviceText{text, n}};
+  const DeviceText src{text, n};
   const uint64_t n_long = *S.long_count;
   const int lane = lane_id();
   const uint64_t waves = static_cast<uint64_t>(gridDim.x) * kWaves;
@@ -107,7 +74,7 @@ __global__ __launch_bounds__(kThreads) void record_group_hash_long_kernel(const 
     const uint64_t j = S.long_list[i];
     const uint64_t r = R.record(j);
     const uint64_t rb = R.rec_begin[r], len = R.rec_end[r] - rb;
-    const uint64_t part = group::hash_groups(src, n, rb, len, static_cast<uint64_t>(lane), kWave, group::n_groups(len));
+    const uint64_t part = group::hash_groups(src, n, rb, len, static_cast<uint64_t>(lane), kWave, rows::n_groups(len));
     const uint64_t sum = wave_sum64(part);
     if (lane == 0) S.hash[j] = group::keep_bits(group::finalize(len, sum), hash_bits);
   }
@@ -129,7 +96,7 @@ template <bool kPeel>
 __global__ __launch_bounds__(kThreads) void record_group_insert_kernel(const uint8_t* __restrict__ text, uint64_t n, Rows R, uint64_t k, uint64_t n_units,
                                                                        uint32_t long_bytes, Scratch S, const unsigned long long* summary) {
   if (refused(summary)) return;
-  const GroupText src{DeviceText{text, n}};
+  const DeviceText src{text, n};
   LaneMem M{S};
   for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
     const uint64_t j = unit * kThreads + threadIdx.x;
@@ -142,7 +109,7 @@ __global__ __launch_bounds__(kThreads) void record_group_insert_kernel(const uin
     uint64_t s = 0;
     if (active) {
       const uint64_t rb = R.rec_begin[R.record(j)];
-      const uint64_t groups = group::n_groups(len);
+      const uint64_t groups = rows::n_groups(len);
       s = group::find_slot(M, j, S.hash[j], len, S.T,
                            [&](uint64_t i) { return group::groups_equal(src, n, R.rec_begin[R.record(i)], rb, len, 0, 1, groups); });
       S.slot_of[j] = static_cast<uint32_t>(s);
@@ -189,7 +156,7 @@ struct WaveMem {
 __global__ __launch_bounds__(kThreads) void record_group_insert_long_kernel(const uint8_t* __restrict__ text, uint64_t n, Rows R, Scratch S,
                                                                             const unsigned long long* summary) {
   if (refused(summary)) return;
-  const GroupText src{DeviceText{text, n}};
+  const DeviceText src{text, n};
   WaveMem M{S};
   const uint64_t n_long = *S.long_count;
   const int lane = lane_id();
@@ -198,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void record_group_insert_long_kernel(cons
     const uint64_t j = S.long_list[i];
     const uint64_t r = R.record(j);
     const uint64_t rb = R.rec_begin[r], len = R.rec_end[r] - rb;
-    const uint64_t groups = group::n_groups(len);
+    const uint64_t groups = rows::n_groups(len);
     // (the stored length saturates: the tables have the length of a row of 4 GiB)
     const auto equal = [&](uint64_t c) {
       const uint64_t rc = R.record(c);
@@ -220,21 +187,13 @@ __global__ __launch_bounds__(kThreads) void record_group_insert_long_kernel(cons
 
 // ---------------------------------------------------------------------------------------------------------------- host
 // the test knobs, read at every call: RJ_GROUP_HASH_BITS (0..64), RJ_GROUP_LONG_BYTES; RJ_GROUP_PEEL=0 is the probe's
-inline uint32_t env_number(const char* name, uint32_t otherwise, uint32_t most) {
-  const char* v = getenv(name);
-  if (!v || !*v) return otherwise;
-  char* end = nullptr;
-  const unsigned long long x = strtoull(v, &end, 10);
-  if (!end || *end) return otherwise;
-  return x > most ? most : static_cast<uint32_t>(x);
-}
 struct GroupKnobs {
   uint32_t long_bytes, hash_bits;
   bool peel;
 };
 inline GroupKnobs group_knobs() {
   GroupKnobs kn;
-  kn.long_bytes = env_number("RJ_GROUP_LONG_BYTES", group::kLongBytes, group::kMaxLongBytes);
+  kn.long_bytes = env_number("RJ_GROUP_LONG_BYTES", group::kLongBytes, rows::kMaxLongBytes);
   kn.hash_bits = env_number("RJ_GROUP_HASH_BITS", 64, 64);
   kn.peel = env_number("RJ_GROUP_PEEL", 1, 1) != 0;
   return kn;

@@ -2,7 +2,7 @@
 // rows of one record table (the PROBE rows, over one text) looked up in the rows of another (the SET rows, over a text of
 // their own) -- Arrow's index_in / is_in, `grep -F -x -f`, a semi-, anti- or inner join on a string key -- exactly.  Host and
 // device code: the CPU tests drive exactly these functions (tests/support/lookup_exec.cc) through two Text policies and a Mem
-// policy, as the kernels do.
+// policy, as the kernels do.  The byte compare across the two texts is record_rows.h's group_equal / groups_equal.
 //
 // The set side is record_group.h's table, built by its hash and insert passes over the set rows, unchanged.  A row's hash
 // depends on its bytes and length alone -- not on its alignment, not on its text -- so a probe row hashed in ITS text starts
@@ -32,7 +32,7 @@ constexpr uint64_t kAbsent = ~0ull;        // probe_slot: the string is in no sl
 constexpr uint32_t kStagedNone = ~0u;      // a staged answer: set rows are below 2^31
 
 // ---------------------------------------------------------------------------------------------------------------- limits
-RJ_PACK_HD inline bool rows_fit(uint64_t ks, uint64_t kp) { return group::rows_fit(ks) && group::rows_fit(kp); }
+RJ_PACK_HD inline bool rows_fit(uint64_t ks, uint64_t kp) { return rows::rows_fit(ks) && rows::rows_fit(kp); }
 
 // The scratch of a call, in bytes from the buffer's begin (every part 16-byte aligned): group::layout(ks) for the set side
 // (44 .. 68 bytes per set row); `hits`, one 32-bit count per slot (4 bytes per slot: 8 .. 16 per set row); and for the probe
@@ -45,12 +45,13 @@ struct Layout {
   uint64_t hits, staged, long_list, bytes;
 };
 RJ_PACK_HD inline Layout layout(uint64_t ks, uint64_t kp) {
+  using rows::align16;
   Layout l;
   l.set = group::layout(ks);
-  l.hits = group::align16(l.set.bytes);
-  l.staged = l.hits + group::align16(4 * group::table_slots(ks));
-  l.long_list = l.staged + group::align16(4 * kp);
-  l.bytes = l.long_list + group::align16(4 * kp);
+  l.hits = align16(l.set.bytes);
+  l.staged = l.hits + align16(4 * group::table_slots(ks));
+  l.long_list = l.staged + align16(4 * kp);
+  l.bytes = l.long_list + align16(4 * kp);
   return l;
 }
 RJ_PACK_HD inline uint64_t widen(uint32_t staged) { return staged == kStagedNone ? kNone : static_cast<uint64_t>(staged); }
@@ -72,24 +73,10 @@ RJ_PACK_HD inline uint64_t probe_slot(Mem& M, uint64_t h, uint32_t len32, uint64
   }
 }
 
-// group g of two rows of the same length, row a in the set text (of set_n bytes) and row b in the probe text (of n bytes):
-// equal?  Each side takes its guarded load at its OWN text's end.
-template <class SetText, class Text>
-RJ_PACK_HD inline bool group_equal(const SetText& set_text, uint64_t set_n, uint64_t a, const Text& text, uint64_t n, uint64_t b, uint64_t len, uint64_t g) {
-  uint32_t x[4], y[4];
-  group::load_group(set_text, set_n, a, len, g, x);
-  group::load_group(text, n, b, len, g, y);
-  return ((x[0] ^ y[0]) | (x[1] ^ y[1]) | (x[2] ^ y[2]) | (x[3] ^ y[3])) == 0;
-}
-// ... the groups g0, g0 + stride, ... below g_end (a lane walks a short row with g0 = 0, stride = 1; a lane of the wave tier
-// with g0 = its number, stride = 64).  No shortcut for a == b: the offsets belong to two texts.
-template <class SetText, class Text>
-RJ_PACK_HD inline bool groups_equal(const SetText& set_text, uint64_t set_n, uint64_t a, const Text& text, uint64_t n, uint64_t b, uint64_t len, uint64_t g0,
-                                    uint64_t stride, uint64_t g_end) {
-  for (uint64_t g = g0; g < g_end; g += stride)
-    if (!group_equal(set_text, set_n, a, text, n, b, len, g)) return false;
-  return true;
-}
+// The byte compare of set row a (in the set text) and probe row b (in the probe text): record_rows.h's two-text group_equal /
+// groups_equal, under this header's names too.  No shortcut for a == b: the offsets belong to two texts.
+using rows::group_equal;
+using rows::groups_equal;
 
 // ---------------------------------------------------------------------------------------------------------------- hits
 // set row i behind all probes: its string's hit count when it is the smallest row of its string, else 0

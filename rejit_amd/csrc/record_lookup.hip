@@ -5,10 +5,11 @@
 // why the probes need nothing but plain loads; four or five memsets and up to eight launches on one stream, one synchronise:
 //
 // Build: record_group_build.h's hash, hash-long, insert and insert-long kernels over the SET table -- rj_scan_records_group's own.
-// Probe (lane): one probe row per lane.  The pack's checks (the first bad row wins by one atomic max, in a summary word of
-//   the probe side's own); rows of at most L bytes are hashed and looked up at once -- the probe side stores no hash and no
-//   length --, longer ones are appended to a list (one ballot, one atomic add per wave).  One unit of 256 rows per workgroup.  The byte compare covers at most L
-//   bytes and reads both texts.  The answer is staged as a 32-bit word (record_lookup.h: a refused call writes no output row).
+// Probe (lane): one probe row per lane.  The pack's checks (rows::resolve; the first bad row wins, note_bad_row, in a summary
+//   word of the probe side's own); rows of at most L bytes are hashed and looked up at once -- the probe side stores no hash
+//   and no length --, longer ones are appended to a list (wave_append).  One unit of 256 rows per workgroup.  The byte compare
+//   covers at most L bytes and reads both texts (rows::groups_equal).  The answer is staged as a 32-bit word (record_lookup.h:
+//   a refused call writes no output row).
 //   With hit counts the lanes that ended at the slot of the wave's first found lane issue ONE atomic add (the peel), the
 //   others their own; without them (the is_in path: neither d_set_hits nor stats) the kernel issues no atomic on the table or
 //   the counts.
@@ -18,7 +19,7 @@
 // Hits: one lane per set row: d_set_hits[i] = hits[slot_of[i]] when slot[slot_of[i]] == i, else 0; n_set_distinct and
 //   n_set_hit from ballots, one atomic add per wave.
 // Every kernel behind the first check returns at once when the summary holds a bad row of either table.  Nothing here waits
-// for another lane's progress.
+// for another lane's progress.  The rows, the text, the refusal and the two wave idioms are record_frame.h's.
 #include <hip/hip_runtime.h>
 
 #include "engine_internal.h"
@@ -26,7 +27,7 @@
 #include "record_group.h"
 #include "record_group_build.h"
 #include "record_lookup.h"
-#include "record_pack.h"
+#include "record_rows.h"
 
 namespace rejit_amd {
 
@@ -75,51 +76,37 @@ struct ProbeWaveMem {
 
 // ---------------------------------------------------------------------------------------------------------------- probe
 template <bool kHits, bool kPeel>
-__global__ __launch_bounds__(kThreads) void record_lookup_probe_kernel(const uint8_t* __restrict__ set_text, uint64_t set_n,
-                                                                       const uint64_t* __restrict__ set_begin, const uint64_t* __restrict__ set_indices,
+__global__ __launch_bounds__(kThreads) void record_lookup_probe_kernel(const uint8_t* __restrict__ set_text, uint64_t set_n, Rows RS,
                                                                        const uint8_t* __restrict__ text, uint64_t n, Rows R, uint64_t n_records, uint64_t kp,
                                                                        uint32_t long_bytes, uint32_t hash_bits, SetTable S, ProbeScratch P,
                                                                        unsigned long long* summary) {
   if (refused(summary)) return;   // a bad set row: the set table is checked first, and its row is the one the call names
-  const GroupText set_src{DeviceText{set_text, set_n}};
-  const GroupText src{DeviceText{text, n}};
+  const DeviceText set_src{set_text, set_n};
+  const DeviceText src{text, n};
   ProbeLaneMem M{S};
   // one unit of 256 rows per workgroup (no persistent loop: what the checks and the hash need is dead when the walk begins)
   const uint64_t j = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x;
   bool bad = false, is_long = false, found = false;
   uint64_t s = 0;
   if (j < kp) {
-    const uint64_t r = R.record(j);
-    bad = pack::bad_index(r, n_records);
-    uint64_t rb = 0, re = 0;
+    const rows::Row row = rows::resolve(R.rec_begin, R.rec_end, R.indices, n_records, n, j);
+    bad = row.bad;
     if (!bad) {
-      rb = R.rec_begin[r], re = R.rec_end[r];
-      bad = pack::bad_row(rb, re, n);
-    }
-    if (!bad) {
-      const uint64_t len = re - rb;
+      const uint64_t rb = row.rb, len = row.len();
       is_long = len > long_bytes;
       if (!is_long) {
         const uint64_t h = group::keep_bits(group::hash_row(src, n, rb, len), hash_bits);
-        const uint64_t groups = group::n_groups(len);
+        const uint64_t groups = rows::n_groups(len);
         s = lookup::probe_slot(M, h, static_cast<uint32_t>(len), S.slot_count(), [&](uint64_t i) {
-          return lookup::groups_equal(set_src, set_n, set_begin[set_indices ? set_indices[i] : i], src, n, rb, len, 0, 1, groups);
+          return rows::groups_equal(set_src, set_n, RS.rec_begin[RS.record(i)], src, n, rb, len, 0, 1, groups);
         });
         found = s != lookup::kAbsent;
         P.staged[j] = found ? static_cast<uint32_t>(M.slot_load(s)) : lookup::kStagedNone;
       }
     }
   }
-  const uint64_t bad_lanes = __ballot(bad);
-  if (bad_lanes && lane_id() == __builtin_ctzll(bad_lanes)) atomicMax(&summary[kSumProbeBad], static_cast<unsigned long long>(~j));
-  const uint64_t long_lanes = __ballot(is_long);
-  if (long_lanes) {
-    const int leader = __builtin_ctzll(long_lanes);
-    unsigned long long base = 0;
-    if (lane_id() == leader) base = atomicAdd(&summary[kSumLongRows], static_cast<unsigned long long>(__popcll(long_lanes)));
-    base = lane_value(base, leader);
-    if (is_long) P.long_list[base + lanes_below(long_lanes)] = static_cast<uint32_t>(j);
-  }
+  note_bad_row(bad, j, &summary[kSumProbeBad]);
+  wave_append(is_long, static_cast<uint32_t>(j), &summary[kSumLongRows], P.long_list);
   if (kHits) {
     const uint64_t found_lanes = __ballot(found);
     if (!found_lanes) return;
@@ -141,8 +128,8 @@ __global__ __launch_bounds__(kThreads) void record_lookup_probe_long_kernel(cons
                                                                             const uint8_t* __restrict__ text, uint64_t n, Rows R, uint32_t hash_bits, SetTable S,
                                                                             ProbeScratch P, const unsigned long long* summary) {
   if (lookup_refused(summary)) return;
-  const GroupText set_src{DeviceText{set_text, set_n}};
-  const GroupText src{DeviceText{text, n}};
+  const DeviceText set_src{set_text, set_n};
+  const DeviceText src{text, n};
   ProbeWaveMem M{S};
   const uint32_t n_long = static_cast<uint32_t>(summary[kSumLongRows]);   // (at most kp < 2^31; the grid has at most 1024 x 4 waves)
   const int lane = lane_id();
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(kThreads) void record_lookup_probe_long_kernel(cons
     const uint64_t j = P.long_list[i];
     const uint64_t r = R.record(j);
     const uint64_t rb = R.rec_begin[r], len = R.rec_end[r] - rb;
-    const uint64_t groups = group::n_groups(len);
+    const uint64_t groups = rows::n_groups(len);
     const uint64_t part = group::hash_groups(src, n, rb, len, static_cast<uint64_t>(lane), kWave, groups);
     const uint64_t h = group::keep_bits(group::finalize(len, wave_sum64(part)), hash_bits);
     // (the stored length saturates: the tables have the length of a row of 4 GiB)
@@ -162,7 +149,7 @@ __global__ __launch_bounds__(kThreads) void record_lookup_probe_long_kernel(cons
       if (RS.rec_end[rc] - cb != len) return false;
       for (uint64_t g0 = 0; g0 < groups; g0 += kWave) {
         const uint64_t g = g0 + static_cast<uint64_t>(lane);
-        const bool differs = g < groups && !lookup::group_equal(set_src, set_n, cb, src, n, rb, len, g);
+        const bool differs = g < groups && !rows::group_equal(set_src, set_n, cb, src, n, rb, len, g);
         if (__ballot(differs)) return false;
       }
       return true;
@@ -270,7 +257,7 @@ int64_t rj_scan_records_lookup(rj_scan* s, const void* d_set_text, uint64_t set_
   const dim3 grid(unit_grid(units)), block(kThreads);
 #define RJ_LOOKUP_PROBE(HITS, PEEL)                                                                                                           \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(record_lookup_probe_kernel<HITS, PEEL>), dim3(static_cast<unsigned>(units ? units : 1)), block, 0, st, set_text, \
-                     set_n, d_set_begin, d_set_indices, text, n, R, n_records, kp, knobs.long_bytes, knobs.hash_bits, table, P, summary)
+                     set_n, RS, text, n, R, n_records, kp, knobs.long_bytes, knobs.hash_bits, table, P, summary)
   if (!want_hits) RJ_LOOKUP_PROBE(false, false);
   else if (knobs.peel) RJ_LOOKUP_PROBE(true, true);
   else RJ_LOOKUP_PROBE(true, false);

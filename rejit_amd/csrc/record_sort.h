@@ -1,7 +1,7 @@
 // rejit_amd/csrc/record_sort.h -- the arithmetic of rj_scan_records_sort (record_sort.hip): the rows of a record table put in
 // the order of their BYTES -- memcmp's order, a proper prefix first, equal rows in ascending j: `LC_ALL=C sort -s`.  Host and
 // device code: the CPU tests drive exactly these functions (tests/support/sort_exec.cc) through a Text and a Mem policy, as
-// the kernels do.
+// the kernels do.  The limits, the guarded 16-byte load and the Text policy are record_rows.h's.
 //
 // Row j is text[rb, re) of record r(j).  Its key at depth d, with c = min(len - d, 7) bytes left there:
 //     key(row, d) = the c bytes row[d ..] big-endian in the upper 56 bits, zero-padded | c in the low 8 bits
@@ -34,21 +34,21 @@
 #include <stdint.h>
 
 #include "record_pack.h"
+#include "record_rows.h"
 
 namespace rejit_amd {
 namespace sort {
 
 constexpr uint64_t kWindow = 7;                  // bytes of a row a key holds
-constexpr uint64_t kGroupBytes = 16;             // bytes a compare step reads of either row
-constexpr uint64_t kMaxRows = 1ull << 31;        // rows, positions and segments share 32-bit words in the scratch
+using rows::kGroupBytes;                         // bytes a compare step reads of either row
 constexpr uint32_t kLongBytes = 64;              // the prefix skip's lane tier stops after this many bytes (RJ_SORT_LONG_BYTES)
-constexpr uint32_t kMaxLongBytes = 1u << 20;
 constexpr uint64_t kNoDepth = ~0ull;
 constexpr uint8_t kHead = 1, kOpen = 2;          // a position's flags
 
 // ---------------------------------------------------------------------------------------------------------------- limits
-RJ_PACK_HD inline bool rows_fit(uint64_t k) { return k < kMaxRows; }
-// an open segment has at least two rows: at most k / 2 of them, and one in the first round
+// A call takes rows_fit(k) rows: rows, positions and segments share 32-bit words in the scratch.
+using rows::rows_fit;
+// An open segment has at least two rows: at most k / 2 of them, and one in the first round
 RJ_PACK_HD inline uint64_t max_segments(uint64_t k) { return k / 2 > 1 ? k / 2 : 1; }
 // The scratch of a call, in bytes from the buffer's begin (every part 16-byte aligned).  Per row: the flags (1), perm (4),
 // the depth a position's segment has when it heads one (8), the active list's positions (4), keys and (segment, row) words
@@ -58,8 +58,8 @@ RJ_PACK_HD inline uint64_t max_segments(uint64_t k) { return k / 2 > 1 ? k / 2 :
 struct Layout {
   uint64_t flags, perm, pos_depth, act_pos, key_a, key_b, segrow_a, segrow_b, long_list, seg_depth, seg_cur, seg_head, bytes;
 };
-RJ_PACK_HD inline uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
 RJ_PACK_HD inline Layout layout(uint64_t k) {
+  using rows::align16;
   const uint64_t S = max_segments(k);
   Layout l;
   l.flags = 0;
@@ -86,13 +86,6 @@ RJ_PACK_HD inline unsigned seg_bits(uint64_t n_segments) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- key
-// text[s, s + 16) as four little-endian words, zero behind the text's end.  Text: load16(s, w) reads 16 bytes all inside
-// [0, n); load16_guarded(s, w) reads the bytes below n one by one -- taken where 16 bytes would reach outside the text.
-template <class Text>
-RJ_PACK_HD inline void load_at(const Text& text, uint64_t n, uint64_t s, uint32_t w[4]) {
-  if (s + kGroupBytes <= n) text.load16(s, w);
-  else text.load16_guarded(s, w);
-}
 RJ_PACK_HD inline uint64_t byte_swap(uint64_t v) {
   v = ((v & 0x00FF00FF00FF00FFull) << 8) | ((v >> 8) & 0x00FF00FF00FF00FFull);
   v = ((v & 0x0000FFFF0000FFFFull) << 16) | ((v >> 16) & 0x0000FFFF0000FFFFull);
@@ -106,7 +99,7 @@ RJ_PACK_HD inline uint64_t key(const Text& text, uint64_t n, uint64_t begin, uin
   const uint64_t c = window_bytes(len, d);
   if (c == 0) return 0;
   uint32_t w[4];
-  load_at(text, n, begin + d, w);
+  rows::load_at(text, n, begin + d, w);
   const uint64_t be = byte_swap(static_cast<uint64_t>(w[0]) | (static_cast<uint64_t>(w[1]) << 32));   // the first byte on top
   return (be & (~0ull << (8 * (8 - c)))) | c;
 }
@@ -117,8 +110,8 @@ RJ_PACK_HD inline uint64_t key(const Text& text, uint64_t n, uint64_t begin, uin
 template <class Text>
 RJ_PACK_HD inline uint32_t group_agree(const Text& text, uint64_t n, uint64_t a, uint64_t b, uint32_t valid) {
   uint32_t x[4], y[4];
-  load_at(text, n, a, x);
-  load_at(text, n, b, y);
+  rows::load_at(text, n, a, x);
+  rows::load_at(text, n, b, y);
   uint32_t at = 16;
   for (int i = 3; i >= 0; i--) {
     const uint32_t d = x[i] ^ y[i];

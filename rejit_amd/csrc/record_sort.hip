@@ -4,18 +4,19 @@
 // record_sort.h has the arithmetic: a most-significant-first refinement over 7-byte windows with a common-prefix skip.  A round
 // is these launches on one stream and ONE synchronise, which brings back the numbers of open rows and open segments:
 //
-// Init (first round only): the pack's checks (the first bad row wins by one atomic max); perm = the identity, one open segment.
+// Init (first round only): the pack's checks (rows::resolve; the first bad row wins, note_bad_row); perm = the identity, one
+//   open segment.
 // Compact: record_frame.h's unit scan over the positions' flags -> the dense list of open (position, segment, row).
 // Skip (lane), from the second round on: one listed row per lane against its segment's first row, at most L bytes; one
 //   atomic min into the segment's depth where the lane knows less than the word says; rows that agreed on all L bytes and
-//   have more are appended to a list (one ballot, one atomic add per wave).
+//   have more are appended to a list (wave_append).
 // Skip (wave): one wave per such row, 64 lanes x 16 bytes = 1 KiB per iteration, a ballot ends it at the first difference.
 // Key: one listed row per lane, key(row, depth of its segment) beside the row.
 // Order: rocPRIM's radix sort, stable: by key, then -- when there is more than one segment -- by the bits of the segment number.
 // Cut: one sorted entry per lane: the new flags of its position; a position that closes gets its d_order row, ONCE.
 // Every kernel behind the first returns at once when the summary holds a bad row: a refused call writes no output row.
+// The rows, the text, the refusal, the two wave idioms and the knobs' parser are record_frame.h's.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include <cstring>  // must precede rocprim (its texture iterator uses ::memset)
 
@@ -23,7 +24,7 @@
 
 #include "engine_internal.h"
 #include "record_frame.h"
-#include "record_pack.h"
+#include "record_rows.h"
 #include "record_sort.h"
 
 namespace rejit_amd {
@@ -32,24 +33,6 @@ namespace {
 
 // the words of the call's summary a round leaves: open rows and open segments behind its cut, the rows its wave tier took
 enum { kSortOpenRows = kSumKept, kSortOpenSegments = kSumMatching, kSortLongRows = kSumCrossing };
-
-// record_sort.h's Text over record_frame.h's DeviceText
-struct SortText {
-  DeviceText t;
-  __device__ __forceinline__ void load16(uint64_t s, uint32_t w[4]) const { t.load16(s, w); }
-  __device__ __forceinline__ void load16_guarded(uint64_t s, uint32_t w[4]) const {
-    uint32_t d[6];
-    load_guarded(t.text, t.n, s, d);
-    w[0] = d[0], w[1] = d[1], w[2] = d[2], w[3] = d[3];
-  }
-};
-
-struct Rows {
-  const uint64_t* __restrict__ rec_begin;
-  const uint64_t* __restrict__ rec_end;
-  const uint64_t* __restrict__ indices;
-  __device__ __forceinline__ uint64_t record(uint64_t j) const { return indices ? indices[j] : j; }
-};
 
 // the scratch of a call (sort::layout)
 struct Scratch {
@@ -72,8 +55,6 @@ struct SortedList {
   __device__ __forceinline__ uint64_t key(uint64_t i) const { return keys[i]; }
 };
 
-__device__ __forceinline__ bool refused(const unsigned long long* summary) { return summary[kSumBadWord] != 0 || summary[kSumTimedOut] != 0; }
-
 // ---------------------------------------------------------------------------------------------------------------- init
 __global__ __launch_bounds__(kThreads) void record_sort_init_kernel(uint64_t n, Rows R, uint64_t n_records, uint64_t k, uint64_t n_units, Scratch S,
                                                                     uint64_t* __restrict__ order, unsigned long long* summary) {
@@ -81,16 +62,13 @@ __global__ __launch_bounds__(kThreads) void record_sort_init_kernel(uint64_t n, 
     const uint64_t j = unit * kThreads + threadIdx.x;
     bool bad = false;
     if (j < k) {
-      const uint64_t r = R.record(j);
-      bad = pack::bad_index(r, n_records);
-      if (!bad) bad = pack::bad_row(R.rec_begin[r], R.rec_end[r], n);
+      bad = rows::resolve(R.rec_begin, R.rec_end, R.indices, n_records, n, j).bad;
       S.perm[j] = static_cast<uint32_t>(j);
       S.flags[j] = k < 2 ? 0 : static_cast<uint8_t>(sort::kOpen | (j == 0 ? sort::kHead : 0));
       if (j == 0) S.pos_depth[0] = 0;
       if (k == 1 && !bad) order[0] = 0;   // (one row: nothing to compare)
     }
-    const uint64_t bad_lanes = __ballot(bad);
-    if (bad_lanes && lane_id() == __builtin_ctzll(bad_lanes)) atomicMax(&summary[kSumBadWord], static_cast<unsigned long long>(~j));
+    note_bad_row(bad, j, &summary[kSumBadWord]);
   }
 }
 
@@ -98,6 +76,9 @@ __global__ __launch_bounds__(kThreads) void record_sort_init_kernel(uint64_t n, 
 __global__ __launch_bounds__(kThreads) void record_sort_compact_kernel(uint64_t k, uint64_t n_units, bool skip, Scratch S, unsigned long long* granules,
                                                                        unsigned long long* ticket, unsigned long long* summary) {
   __shared__ UnitSum s_unit;
+  // Only the bad word, not refused(): kSumTimedOut is written by this kernel's own unit scan and by nothing before it in the
+  // call, so it can be set here only by another workgroup of this launch -- and a workgroup that starts behind a time-out
+  // still takes its units and publishes them (nobody waits on words it left out); the call fails at its end either way.
   if (summary[kSumBadWord] != 0) return;
   unit_init(s_unit.place);
   for (uint64_t tk; unit_take(s_unit.place, ticket, n_units, &tk);) {
@@ -143,7 +124,7 @@ __device__ __forceinline__ void depth_min(unsigned long long* word, uint64_t dep
 __global__ __launch_bounds__(kThreads) void record_sort_skip_kernel(const uint8_t* __restrict__ text, uint64_t n, Rows R, uint64_t n_active, uint64_t n_units,
                                                                     uint32_t long_bytes, Scratch S, unsigned long long* summary) {
   if (refused(summary)) return;
-  const SortText src{DeviceText{text, n}};
+  const DeviceText src{text, n};
   for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
     const uint64_t a = unit * kThreads + threadIdx.x;
     bool more = false;
@@ -152,21 +133,14 @@ __global__ __launch_bounds__(kThreads) void record_sort_skip_kernel(const uint8_
       const uint64_t depth = sort::skip_row(src, n, q.hb, q.hl, q.rb, q.rl, q.D, long_bytes, &more);
       if (!more) depth_min(&S.seg_cur[q.seg], depth);   // (a listed row's word comes from its wave: the segment's depth stays exact)
     }
-    const uint64_t more_lanes = __ballot(more);
-    if (more_lanes) {
-      const int leader = __builtin_ctzll(more_lanes);
-      unsigned long long base = 0;
-      if (lane_id() == leader) base = atomicAdd(&summary[kSortLongRows], static_cast<unsigned long long>(__popcll(more_lanes)));
-      base = lane_value(base, leader);
-      if (more) S.long_list[base + lanes_below(more_lanes)] = static_cast<uint32_t>(a);
-    }
+    wave_append(more, static_cast<uint32_t>(a), &summary[kSortLongRows], S.long_list);
   }
 }
 
 __global__ __launch_bounds__(kThreads) void record_sort_skip_long_kernel(const uint8_t* __restrict__ text, uint64_t n, Rows R, uint32_t long_bytes, Scratch S,
                                                                          const unsigned long long* summary) {
   if (refused(summary)) return;
-  const SortText src{DeviceText{text, n}};
+  const DeviceText src{text, n};
   const uint64_t n_long = summary[kSortLongRows];
   const int lane = lane_id();
   const uint64_t waves = static_cast<uint64_t>(gridDim.x) * kWaves;
@@ -190,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void record_sort_skip_long_kernel(const u
 __global__ __launch_bounds__(kThreads) void record_sort_key_kernel(const uint8_t* __restrict__ text, uint64_t n, Rows R, uint64_t n_active, uint64_t n_units,
                                                                    Scratch S, const unsigned long long* summary) {
   if (refused(summary)) return;
-  const SortText src{DeviceText{text, n}};
+  const DeviceText src{text, n};
   for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
     const uint64_t a = unit * kThreads + threadIdx.x;
     if (a >= n_active) continue;
@@ -234,16 +208,6 @@ __global__ __launch_bounds__(kThreads) void record_sort_cut_kernel(uint64_t n_ac
   }
 }
 
-// the test knobs, read at every call: RJ_SORT_LONG_BYTES, RJ_SORT_SKIP=0
-uint32_t env_number(const char* name, uint32_t otherwise, uint32_t most) {
-  const char* v = getenv(name);
-  if (!v || !*v) return otherwise;
-  char* end = nullptr;
-  const unsigned long long x = strtoull(v, &end, 10);
-  if (!end || *end) return otherwise;
-  return x > most ? most : static_cast<uint32_t>(x);
-}
-
 // the stable sort of the list's n_active entries by (segment, key): key_a / segrow_a -> *keys / *seg_rows
 int order_list(rj_scan* s, const sort::Layout& lay, uint8_t* base, uint64_t n_active, uint64_t n_segments, hipStream_t st, const uint64_t** keys,
                const uint64_t** seg_rows) {
@@ -280,11 +244,12 @@ int64_t rj_scan_records_sort(rj_scan* s, const void* d_text, uint64_t n, const u
   if (!s || (!d_text && n) || (n_records && (!d_rec_begin || !d_rec_end)) || (k && !d_order))
     return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records_sort: null argument");
   if (!aligned8(d_rec_begin, d_rec_end, d_indices, d_order)) return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records_sort: a table is not 8-byte aligned");
-  if (!sort::rows_fit(k))
+  if (!rows::rows_fit(k))
     return rj_fail(RJ_TOO_LARGE, "rj_scan_records_sort: %llu rows: rows and segments share 32-bit words in the scratch (fewer than 2^31 rows)",
                    static_cast<unsigned long long>(k));
   if (k == 0) return 0;
-  const uint32_t long_bytes = env_number("RJ_SORT_LONG_BYTES", sort::kLongBytes, sort::kMaxLongBytes);
+  // the test knobs, read at every call: RJ_SORT_LONG_BYTES, RJ_SORT_SKIP=0
+  const uint32_t long_bytes = env_number("RJ_SORT_LONG_BYTES", sort::kLongBytes, rows::kMaxLongBytes);
   const bool skip = env_number("RJ_SORT_SKIP", 1, 1) != 0;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   const uint64_t n_units = (k + kThreads - 1) / kThreads;

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kThreads) void record_split_emit_kernel(DeviceMem M
                                                                      const unsigned long long* summary) {
   __shared__ EmitStage s_stage;
   __shared__ uint64_t s_rows[2];
-  if (summary[kSumBadWord] != 0 || summary[kSumTimedOut] != 0) return;   // a refused plan: its tables are not followed anywhere
+  if (refused(summary)) return;
   const uint64_t total = summary[kSumTotal];
   const uint64_t limit = total < piece_cap ? total : piece_cap;
   const uint64_t n_chunks = (limit + chunk - 1) / chunk;

@@ -1,6 +1,7 @@
-// tests/support/checked_text.h -- TEST-ONLY: what the drivers of the record pack and the record replace (pack_exec.cc,
-// replace_exec.cc) share: the text both copies read, every access checked against its range, and the store of a 16-byte
-// group, checked against the output's capacity.
+// tests/support/checked_text.h -- TEST-ONLY: what the drivers of the record headers share: the text they read (the Text policy
+// of record_pack.h's copy and of record_rows.h: pack_exec.cc, replace_exec.cc, group_exec.cc, sort_exec.cc, lookup_exec.cc),
+// every access checked against its range, and the store of a 16-byte group of the pack and the replace, checked against the
+// output's capacity.
 #ifndef REJIT_AMD_TESTS_CHECKED_TEXT_H_
 #define REJIT_AMD_TESTS_CHECKED_TEXT_H_
 
@@ -17,7 +18,7 @@ struct CheckedText {
   const uint8_t* text;
   uint64_t n;
   mutable bool left_range = false;
-  mutable uint64_t loads16 = 0, byte_reads = 0;
+  mutable uint64_t loads16 = 0, byte_reads = 0, guarded = 0;
   uint32_t at(uint64_t s) const {
     if (s >= n) {
       left_range = true;
@@ -25,10 +26,18 @@ struct CheckedText {
     }
     return text ? text[s] : synth(s);
   }
+  // (all 16 bytes inside the text: that is the contract of the device's load16)
   void load16(uint64_t s, uint32_t w[4]) const {
     loads16++;
     for (int i = 0; i < 4; i++) w[i] = 0;
     for (uint32_t b = 0; b < 16; b++) w[b >> 2] |= at(s + b) << (8 * (b & 3));
+  }
+  // the bytes below n, zero behind them
+  void load16_guarded(uint64_t s, uint32_t w[4]) const {
+    guarded++;
+    for (int i = 0; i < 4; i++) w[i] = 0;
+    for (uint32_t b = 0; b < 16; b++)
+      if (s + b < n) w[b >> 2] |= at(s + b) << (8 * (b & 3));
   }
   uint32_t byte(uint64_t s) const {
     byte_reads++;

@@ -13,85 +13,17 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_group.h"
+#include "checked_table.h"
+#include "checked_text.h"
 
 using namespace rejit_amd;
-
-namespace {
-
-struct CheckedText {
-  const uint8_t* text;
-  uint64_t n;
-  mutable bool left_range = false;
-  uint32_t at(uint64_t s) const {
-    if (s >= n) {
-      left_range = true;
-      return 0;
-    }
-    return text[s];
-  }
-  // (all 16 bytes inside the text: that is the contract of the device's load16)
-  void load16(uint64_t s, uint32_t w[4]) const {
-    for (int i = 0; i < 4; i++) w[i] = 0;
-    for (uint32_t b = 0; b < 16; b++) w[b >> 2] |= at(s + b) << (8 * (b & 3));
-  }
-  void load16_guarded(uint64_t s, uint32_t w[4]) const {
-    for (int i = 0; i < 4; i++) w[i] = 0;
-    for (uint32_t b = 0; b < 16; b++)
-      if (s + b < n) w[b >> 2] |= at(s + b) << (8 * (b & 3));
-  }
-};
-
-struct CheckedMem {
-  std::vector<uint64_t> slots;
-  std::vector<uint32_t> slot_count, slot_group, len, slot_of;
-  std::vector<uint64_t> hash;
-  bool left_range = false;
-  uint64_t probes = 0;
-  bool slot_ok(uint64_t s) {
-    if (s >= slots.size()) left_range = true;
-    return s < slots.size();
-  }
-  bool row_ok(uint64_t i) {
-    if (i >= hash.size()) left_range = true;
-    return i < hash.size();
-  }
-  uint64_t slot_load(uint64_t s) {
-    probes++;
-    return slot_ok(s) ? slots[s] : 0;
-  }
-  uint64_t slot_cas(uint64_t s, uint64_t j) {
-    if (!slot_ok(s)) return 0;
-    const uint64_t was = slots[s];
-    if (was == group::kEmpty) slots[s] = j;
-    return was;
-  }
-  void slot_min(uint64_t s, uint64_t j) {
-    if (slot_ok(s) && j < slots[s]) slots[s] = j;
-  }
-  void count_add(uint64_t s, uint32_t c) {
-    if (slot_ok(s)) slot_count[s] += c;
-  }
-  uint32_t len_of(uint64_t i) { return row_ok(i) ? len[i] : 0; }
-};
-// (record_group.h asks for M.hash(i) and M.len(i): the vectors have other names)
-struct MemView {
-  CheckedMem& m;
-  uint64_t slot_load(uint64_t s) { return m.slot_load(s); }
-  uint64_t slot_cas(uint64_t s, uint64_t j) { return m.slot_cas(s, j); }
-  void slot_min(uint64_t s, uint64_t j) { m.slot_min(s, j); }
-  void count_add(uint64_t s, uint32_t c) { m.count_add(s, c); }
-  uint64_t hash(uint64_t i) { return m.row_ok(i) ? m.hash[i] : 0; }
-  uint32_t len(uint64_t i) { return m.len_of(i); }
-};
-
-}  // namespace
 
 // The hash of the row [begin, begin + len) with its groups dealt to `lanes` lanes -- strided (lane l: groups l, l + lanes, ...)
 // or blocked (lane l: a contiguous run) -- and the lanes' sums added.  Returns 0, -1 when a read left the text.
 extern "C" long gr_hash(const uint8_t* text, uint64_t n, uint64_t begin, uint64_t len, uint64_t lanes, int blocked, uint32_t bits, uint64_t* out) {
   if (lanes == 0 || begin > n || len > n - begin) return -2;
   const CheckedText T{text, n};
-  const uint64_t groups = group::n_groups(len);
+  const uint64_t groups = rows::n_groups(len);
   const uint64_t per = (groups + lanes - 1) / lanes;
   uint64_t sum = 0;
   for (uint64_t l = 0; l < lanes; l++) {
@@ -113,12 +45,12 @@ extern "C" long gr_rows_equal(const uint8_t* text, uint64_t n, uint64_t a, uint6
   const uint64_t ha = group::keep_bits(group::hash_row(T, n, a, la), bits), hb = group::keep_bits(group::hash_row(T, n, b, lb), bits);
   long r = 0;
   if (group::stored_len(la) == group::stored_len(lb) && ha == hb) r |= 1;
-  if (la == lb && group::groups_equal(T, n, a, b, la, 0, 1, group::n_groups(la))) r |= 2;
+  if (la == lb && group::groups_equal(T, n, a, b, la, 0, 1, rows::n_groups(la))) r |= 2;
   return T.left_range ? -1 : r;
 }
 
 extern "C" uint64_t gr_table_slots(uint64_t k) { return group::table_slots(k); }
-extern "C" int gr_rows_fit(uint64_t k) { return group::rows_fit(k) ? 1 : 0; }
+extern "C" int gr_rows_fit(uint64_t k) { return rows::rows_fit(k) ? 1 : 0; }
 extern "C" uint64_t gr_scratch_bytes(uint64_t k) { return group::layout(k).bytes; }
 
 // summary: [0] G, [1] first bad row (~0: none), [2] slot reads of all probes, [3] slots of the table.  order[0 .. k): the rows
@@ -130,40 +62,34 @@ extern "C" long gr_group(const uint8_t* text, uint64_t n, const uint64_t* rec_be
   for (int i = 0; i < 8; i++) summary[i] = 0;
   summary[1] = ~0ull;
   const uint64_t k = have_indices ? n_indices : n_records;
-  if (!group::rows_fit(k) || unit == 0) return -2;
+  if (!rows::rows_fit(k) || unit == 0) return -2;
   if (k == 0) return 0;
   const CheckedText T{text, n};
   const uint64_t slots = group::table_slots(k);
   summary[3] = slots;
-  CheckedMem mem;
-  mem.slots.assign(slots, group::kEmpty);
-  mem.slot_count.assign(slots, 0);
-  mem.slot_group.assign(slots, 0);
-  mem.hash.assign(k, 0), mem.len.assign(k, 0), mem.slot_of.assign(k, 0);
+  CheckedMem mem(slots, k);
   MemView M{mem};
   // ---- hash: the pack's checks, the first bad row wins
   std::vector<uint64_t> rb(k), ln(k);
   for (uint64_t j = 0; j < k; j++) {
-    const uint64_t r = have_indices ? indices[j] : j;
-    if (pack::bad_index(r, n_records) || pack::bad_row(rec_begin[r], rec_end[r], n)) {
+    const rows::Row row = rows::resolve(rec_begin, rec_end, have_indices ? indices : nullptr, n_records, n, j);
+    if (row.bad) {
       if (summary[1] == ~0ull) summary[1] = j;
       continue;
     }
-    rb[j] = rec_begin[r], ln[j] = rec_end[r] - rec_begin[r];
+    rb[j] = row.rb, ln[j] = row.len();
     mem.len[j] = group::stored_len(ln[j]);
     mem.hash[j] = group::keep_bits(group::hash_row(T, n, rb[j], ln[j]), bits);
   }
   if (T.left_range) return -1;
   if (summary[1] != ~0ull) return 0;   // a refused call: the later kernels return at once
   // ---- insert, one row at a time, the invariants checked behind every step
-  std::vector<uint8_t> seen(k, 0);
+  if (!permutation(order, k)) return -4;
   std::vector<uint64_t> before(slots);
   for (uint64_t step = 0; step < k; step++) {
     const uint64_t j = order[step];
-    if (j >= k || seen[j]) return -4;
-    seen[j] = 1;
     before = mem.slots;
-    const auto equal = [&](uint64_t i) { return group::groups_equal(T, n, rb[i], rb[j], ln[j], 0, 1, group::n_groups(ln[j])); };
+    const auto equal = [&](uint64_t i) { return group::groups_equal(T, n, rb[i], rb[j], ln[j], 0, 1, rows::n_groups(ln[j])); };
     const uint64_t s = group::find_slot(M, j, mem.hash[j], mem.len[j], slots, equal);
     if (s >= slots) return -1;
     group::join_slot(M, s, j, 1);
@@ -214,12 +140,6 @@ extern "C" long gr_group(const uint8_t* text, uint64_t n, const uint64_t* rec_be
 
 namespace {
 
-uint64_t g_rng = 88172645463325252ull;
-uint64_t rnd(uint64_t below) {
-  g_rng ^= g_rng << 13, g_rng ^= g_rng >> 7, g_rng ^= g_rng << 17;
-  return g_rng % below;
-}
-
 // one case: k rows drawn from a pool of d strings (prefixes of one another, a shared 16-byte prefix and another last byte),
 // laid out with 0..3 bytes between them, the last one ending at n; inserted in a random order; against a std::map
 int one_case(uint64_t k, uint64_t d, uint32_t bits, uint64_t unit, bool take) {
@@ -245,13 +165,7 @@ int one_case(uint64_t k, uint64_t d, uint32_t bits, uint64_t unit, bool take) {
   std::vector<uint64_t> idx;
   if (take)
     for (uint64_t i = 0; i < k; i++) idx.push_back(rnd(d));
-  std::vector<uint64_t> order(k);
-  for (uint64_t i = 0; i < k; i++) order[i] = i;
-  for (uint64_t i = k; i > 1; i--) {
-    const uint64_t o = rnd(i);
-    const uint64_t t = order[i - 1];
-    order[i - 1] = order[o], order[o] = t;
-  }
+  const std::vector<uint64_t> order = shuffled(k);
   std::map<std::string, uint64_t> seen;
   std::vector<uint64_t> w_group, w_rep, w_count;
   for (uint64_t j = 0; j < k; j++) {

@@ -15,85 +15,10 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_lookup.h"
+#include "checked_table.h"
+#include "checked_text.h"
 
 using namespace rejit_amd;
-
-namespace {
-
-struct CheckedText {
-  const uint8_t* text;
-  uint64_t n;
-  mutable bool left_range = false;
-  uint32_t at(uint64_t s) const {
-    if (s >= n) {
-      left_range = true;
-      return 0;
-    }
-    return text[s];
-  }
-  // (all 16 bytes inside the text: that is the contract of the device's load16)
-  void load16(uint64_t s, uint32_t w[4]) const {
-    for (int i = 0; i < 4; i++) w[i] = 0;
-    for (uint32_t b = 0; b < 16; b++) w[b >> 2] |= at(s + b) << (8 * (b & 3));
-  }
-  void load16_guarded(uint64_t s, uint32_t w[4]) const {
-    for (int i = 0; i < 4; i++) w[i] = 0;
-    for (uint32_t b = 0; b < 16; b++)
-      if (s + b < n) w[b >> 2] |= at(s + b) << (8 * (b & 3));
-  }
-};
-
-// the set side's scratch; `final`: the build is over, and a write is an error
-struct CheckedMem {
-  std::vector<uint64_t> slots, hash;
-  std::vector<uint32_t> slot_count, len, slot_of, hits;
-  bool left_range = false, wrote_final = false, final = false;
-  bool slot_ok(uint64_t s) {
-    if (s >= slots.size()) left_range = true;
-    return s < slots.size();
-  }
-  bool row_ok(uint64_t i) {
-    if (i >= hash.size()) left_range = true;
-    return i < hash.size();
-  }
-  bool writable() {
-    if (final) wrote_final = true;
-    return !final;
-  }
-  uint64_t slot_load(uint64_t s) { return slot_ok(s) ? slots[s] : 0; }
-  uint64_t slot_cas(uint64_t s, uint64_t j) {
-    if (!writable() || !slot_ok(s)) return 0;
-    const uint64_t was = slots[s];
-    if (was == group::kEmpty) slots[s] = j;
-    return was;
-  }
-  void slot_min(uint64_t s, uint64_t j) {
-    if (writable() && slot_ok(s) && j < slots[s]) slots[s] = j;
-  }
-  void count_add(uint64_t s, uint32_t c) {
-    if (writable() && slot_ok(s)) slot_count[s] += c;
-  }
-};
-struct MemView {
-  CheckedMem& m;
-  uint64_t slot_load(uint64_t s) { return m.slot_load(s); }
-  uint64_t slot_cas(uint64_t s, uint64_t j) { return m.slot_cas(s, j); }
-  void slot_min(uint64_t s, uint64_t j) { m.slot_min(s, j); }
-  void count_add(uint64_t s, uint32_t c) { m.count_add(s, c); }
-  uint64_t hash(uint64_t i) { return m.row_ok(i) ? m.hash[i] : 0; }
-  uint32_t len(uint64_t i) { return m.row_ok(i) ? m.len[i] : 0; }
-};
-
-bool permutation(const uint64_t* order, uint64_t k) {
-  std::vector<uint8_t> seen(k, 0);
-  for (uint64_t i = 0; i < k; i++) {
-    if (order[i] >= k || seen[order[i]]) return false;
-    seen[order[i]] = 1;
-  }
-  return true;
-}
-
-}  // namespace
 
 extern "C" int lk_rows_fit(uint64_t ks, uint64_t kp) { return lookup::rows_fit(ks, kp) ? 1 : 0; }
 // [0] bytes, [1] hits, [2] staged, [3] long_list, [4] the set side's bytes
@@ -108,7 +33,7 @@ extern "C" long lk_rows_equal(const uint8_t* set_text, uint64_t set_n, uint64_t 
   if (lanes == 0 || a > set_n || len > set_n - a || b > n || len > n - b) return -2;
   const CheckedText TS{set_text, set_n}, TP{text, n};
   bool equal = true;
-  for (uint64_t l = 0; l < lanes; l++) equal = lookup::groups_equal(TS, set_n, a, TP, n, b, len, l, lanes, group::n_groups(len)) && equal;
+  for (uint64_t l = 0; l < lanes; l++) equal = rows::groups_equal(TS, set_n, a, TP, n, b, len, l, lanes, rows::n_groups(len)) && equal;
   return (TS.left_range || TP.left_range) ? -1 : equal ? 1 : 0;
 }
 
@@ -131,20 +56,17 @@ extern "C" long lk_lookup(const uint8_t* set_text, uint64_t set_n, const uint64_
   const CheckedText TS{set_text, set_n}, TP{text, n};
   const uint64_t slots = group::table_slots(ks);
   summary[5] = slots;
-  CheckedMem mem;
-  mem.slots.assign(slots, group::kEmpty);
-  mem.slot_count.assign(slots, 0), mem.hits.assign(slots, 0);
-  mem.hash.assign(ks, 0), mem.len.assign(ks, 0), mem.slot_of.assign(ks, 0);
+  CheckedMem mem(slots, ks);
   MemView M{mem};
   // ---- the set side: the group's hash pass (the pack's checks, the first bad row wins) and its inserts, one row at a time
   std::vector<uint64_t> sb(ks), sl(ks);
   for (uint64_t i = 0; i < ks; i++) {
-    const uint64_t r = have_set_indices ? set_indices[i] : i;
-    if (pack::bad_index(r, n_set_records) || pack::bad_row(set_begin[r], set_end[r], set_n)) {
+    const rows::Row row = rows::resolve(set_begin, set_end, have_set_indices ? set_indices : nullptr, n_set_records, set_n, i);
+    if (row.bad) {
       if (summary[1] == ~0ull) summary[1] = i;
       continue;
     }
-    sb[i] = set_begin[r], sl[i] = set_end[r] - set_begin[r];
+    sb[i] = row.rb, sl[i] = row.len();
     mem.len[i] = group::stored_len(sl[i]);
     mem.hash[i] = group::keep_bits(group::hash_row(TS, set_n, sb[i], sl[i]), bits);
   }
@@ -152,7 +74,7 @@ extern "C" long lk_lookup(const uint8_t* set_text, uint64_t set_n, const uint64_
   if (summary[1] != ~0ull) return 0;   // a refused call: the later kernels return at once, the probe rows are not even checked
   for (uint64_t step = 0; step < ks; step++) {
     const uint64_t i = insert_order[step];
-    const auto equal = [&](uint64_t c) { return group::groups_equal(TS, set_n, sb[c], sb[i], sl[i], 0, 1, group::n_groups(sl[i])); };
+    const auto equal = [&](uint64_t c) { return group::groups_equal(TS, set_n, sb[c], sb[i], sl[i], 0, 1, rows::n_groups(sl[i])); };
     const uint64_t s = group::find_slot(M, i, mem.hash[i], mem.len[i], slots, equal);
     if (s >= slots) return -1;
     group::join_slot(M, s, i, 1);
@@ -179,14 +101,14 @@ extern "C" long lk_lookup(const uint8_t* set_text, uint64_t set_n, const uint64_
     uint32_t with_first = 0;
     for (uint64_t at = u0; at < u0 + unit && at < kp; at++) {
       const uint64_t j = probe_order[at];
-      const uint64_t r = have_indices ? indices[j] : j;
-      if (pack::bad_index(r, n_records) || pack::bad_row(rec_begin[r], rec_end[r], n)) {
+      const rows::Row row = rows::resolve(rec_begin, rec_end, have_indices ? indices : nullptr, n_records, n, j);
+      if (row.bad) {
         if (j < summary[2]) summary[2] = j;
         continue;
       }
-      const uint64_t rb = rec_begin[r], len = rec_end[r] - rb;
+      const uint64_t rb = row.rb, len = row.len();
       const uint64_t h = group::keep_bits(group::hash_row(TP, n, rb, len), bits);
-      const auto equal = [&](uint64_t c) { return sl[c] == len && lookup::groups_equal(TS, set_n, sb[c], TP, n, rb, len, 0, 1, group::n_groups(len)); };
+      const auto equal = [&](uint64_t c) { return sl[c] == len && rows::groups_equal(TS, set_n, sb[c], TP, n, rb, len, 0, 1, rows::n_groups(len)); };
       const uint64_t s = lookup::probe_slot(PM, h, group::stored_len(len), slots, equal);
       if (staged_once[j]) twice = true;
       staged_once[j] = 1;
@@ -234,12 +156,6 @@ extern "C" long lk_lookup(const uint8_t* set_text, uint64_t set_n, const uint64_
 
 namespace {
 
-uint64_t g_rng = 88172645463325252ull;
-uint64_t rnd(uint64_t below) {
-  g_rng ^= g_rng << 13, g_rng ^= g_rng >> 7, g_rng ^= g_rng << 17;
-  return g_rng % below;
-}
-
 struct Table {
   std::vector<uint8_t> text;
   std::vector<uint64_t> rb, re, idx;
@@ -264,16 +180,6 @@ void fill(Table& t, const std::vector<std::string>& pool, uint64_t k, bool take,
   }
   if (take)
     for (uint64_t i = 0; i < k; i++) t.idx.push_back(rnd(pool.size()));
-}
-
-std::vector<uint64_t> shuffled(uint64_t k) {
-  std::vector<uint64_t> order(k);
-  for (uint64_t i = 0; i < k; i++) order[i] = i;
-  for (uint64_t i = k; i > 1; i--) {
-    const uint64_t o = rnd(i), t = order[i - 1];
-    order[i - 1] = order[o], order[o] = t;
-  }
-  return order;
 }
 
 // one case: set and probe rows drawn from one pool of d strings (prefixes of one another, another last byte), each table in

@@ -12,13 +12,14 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_replace.h"
+#include "checked_table.h"
 #include "checked_text.h"
 
 using namespace rejit_amd;
 
 namespace {
 
-struct CheckedMem {
+struct CheckedSpans {
   const uint64_t *rb, *re, *first_;
   const uint32_t* counts;
   uint64_t n_records;
@@ -76,7 +77,7 @@ extern "C" long re_replace(const uint8_t* text, uint64_t n, const uint64_t* rec_
     }
     removed += in_unit;
   }
-  const CheckedMem M{rec_begin, rec_end, first, counts, n_records, indices, n_indices, spans, m, table.data(), with, with_len};
+  const CheckedSpans M{rec_begin, rec_end, first, counts, n_records, indices, n_indices, spans, m, table.data(), with, with_len};
   // ---- plan
   std::vector<uint64_t> own_begin(k + 1);
   uint64_t* ob = out_begin ? out_begin : own_begin.data();
@@ -152,12 +153,6 @@ extern "C" int re_sums_fit(uint64_t k, uint64_t n, uint64_t m, uint64_t with_len
 #include <string>
 
 namespace {
-
-uint64_t g_rng = 88172645463325252ull;
-uint64_t rnd(uint64_t below) {
-  g_rng ^= g_rng << 13, g_rng ^= g_rng >> 7, g_rng ^= g_rng << 17;
-  return g_rng % below;
-}
 
 // one case: records of the given sizes (a seam of 0 or 2 text bytes between them), matches planted inside the records, the
 // join by record_join.h's rule, the splice row by row

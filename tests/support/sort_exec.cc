@@ -21,38 +21,15 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_sort.h"
+#include "checked_table.h"
+#include "checked_text.h"
 
 using namespace rejit_amd;
 
 namespace {
 
-struct CheckedText {
-  const uint8_t* text;
-  uint64_t n;
-  mutable bool left_range = false;
-  mutable uint64_t guarded = 0;
-  uint32_t at(uint64_t s) const {
-    if (s >= n) {
-      left_range = true;
-      return 0;
-    }
-    return text[s];
-  }
-  // (all 16 bytes inside the text: that is the contract of the device's load16)
-  void load16(uint64_t s, uint32_t w[4]) const {
-    for (int i = 0; i < 4; i++) w[i] = 0;
-    for (uint32_t b = 0; b < 16; b++) w[b >> 2] |= at(s + b) << (8 * (b & 3));
-  }
-  void load16_guarded(uint64_t s, uint32_t w[4]) const {
-    guarded++;
-    for (int i = 0; i < 4; i++) w[i] = 0;
-    for (uint32_t b = 0; b < 16; b++)
-      if (s + b < n) w[b >> 2] |= at(s + b) << (8 * (b & 3));
-  }
-};
-
 // record_sort.h's Mem: the scratch a position owns and the output, every index checked, an output row written once
-struct CheckedMem {
+struct CheckedPositions {
   std::vector<uint8_t> flags, written;
   std::vector<uint32_t> perm;
   std::vector<uint64_t> pos_depth;
@@ -100,7 +77,7 @@ struct Table {
 };
 
 // P4 over every segment (open and closed): equal rows in ascending j
-bool equal_rows_ascend(const Table& T, const CheckedMem& mem, uint64_t k) {
+bool equal_rows_ascend(const Table& T, const CheckedPositions& mem, uint64_t k) {
   std::map<std::string, uint32_t> last;
   for (uint64_t p = 0; p < k; p++) {
     if (mem.flags[p] & sort::kHead) last.clear();
@@ -124,7 +101,7 @@ extern "C" long so_key(const uint8_t* text, uint64_t n, uint64_t begin, uint64_t
   out[1] = T.guarded;
   return T.left_range ? -1 : 0;
 }
-extern "C" int so_rows_fit(uint64_t k) { return sort::rows_fit(k) ? 1 : 0; }
+extern "C" int so_rows_fit(uint64_t k) { return rows::rows_fit(k) ? 1 : 0; }
 extern "C" uint64_t so_scratch_bytes(uint64_t k) { return sort::layout(k).bytes; }
 extern "C" unsigned so_seg_bits(uint64_t n_segments) { return sort::seg_bits(n_segments); }
 // the lane tier for one pair of rows -> the depth, *more
@@ -145,23 +122,23 @@ extern "C" long so_sort(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
   for (int i = 0; i < 8; i++) summary[i] = 0;
   summary[1] = ~0ull;
   const uint64_t k = have_indices ? n_indices : n_records;
-  if (!sort::rows_fit(k) || unit == 0) return -2;
+  if (!rows::rows_fit(k) || unit == 0) return -2;
   if (k == 0) return 0;
   const CheckedText T{text, n};
   // ---- init: the pack's checks, the first bad row wins
-  Table rows{text, std::vector<uint64_t>(k), std::vector<uint64_t>(k)};
+  Table table{text, std::vector<uint64_t>(k), std::vector<uint64_t>(k)};
   uint64_t max_len = 0;
   for (uint64_t j = 0; j < k; j++) {
-    const uint64_t r = have_indices ? indices[j] : j;
-    if (pack::bad_index(r, n_records) || pack::bad_row(rec_begin[r], rec_end[r], n)) {
+    const rows::Row row = rows::resolve(rec_begin, rec_end, have_indices ? indices : nullptr, n_records, n, j);
+    if (row.bad) {
       if (summary[1] == ~0ull) summary[1] = j;
       continue;
     }
-    rows.rb[j] = rec_begin[r], rows.ln[j] = rec_end[r] - rec_begin[r];
-    if (rows.ln[j] > max_len) max_len = rows.ln[j];
+    table.rb[j] = row.rb, table.ln[j] = row.len();
+    if (table.ln[j] > max_len) max_len = table.ln[j];
   }
   if (summary[1] != ~0ull) return 0;   // a refused call: the later kernels return at once
-  CheckedMem mem;
+  CheckedPositions mem;
   mem.flags.assign(k, 0), mem.written.assign(k, 0), mem.perm.assign(k, 0), mem.pos_depth.assign(k, 0);
   mem.order = out_order;
   for (uint64_t j = 0; j < k; j++) {
@@ -172,9 +149,9 @@ extern "C" long so_sort(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
   // the meaning: the unique stable order
   std::vector<uint32_t> want(k);
   for (uint64_t j = 0; j < k; j++) want[j] = static_cast<uint32_t>(j);
-  std::stable_sort(want.begin(), want.end(), [&](uint32_t a, uint32_t b) { return rows.compare(a, b) < 0; });
+  std::stable_sort(want.begin(), want.end(), [&](uint32_t a, uint32_t b) { return table.compare(a, b) < 0; });
   uint64_t distinct = 1;
-  for (uint64_t i = 1; i < k; i++) distinct += rows.compare(want[i - 1], want[i]) != 0;
+  for (uint64_t i = 1; i < k; i++) distinct += table.compare(want[i - 1], want[i]) != 0;
 
   const uint64_t max_segments = sort::max_segments(k);
   uint64_t n_active = k >= 2 ? k : 0, n_segments = 1;
@@ -182,7 +159,7 @@ extern "C" long so_sort(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
   std::vector<uint64_t> seg_depth(max_segments), seg_cur(max_segments);
   std::vector<Entry> list, before_sort;
   for (bool first = true; n_active; first = false) {
-    if (!equal_rows_ascend(rows, mem, k)) return summary[6] = 4, -3;
+    if (!equal_rows_ascend(table, mem, k)) return summary[6] = 4, -3;
     const bool skips = skip && !first;
     // ---- compact, unit by unit
     list.assign(n_active, Entry{0, 0});
@@ -215,7 +192,7 @@ extern "C" long so_sort(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
         const uint32_t s = sort::seg_of(list[a].seg_row);
         const uint32_t j = sort::row_of(list[a].seg_row), h = sort::row_of(list[seg_head[s]].seg_row);
         bool more = false;
-        const uint64_t depth = sort::skip_row(T, n, rows.rb[h], rows.ln[h], rows.rb[j], rows.ln[j], seg_depth[s], L, &more);
+        const uint64_t depth = sort::skip_row(T, n, table.rb[h], table.ln[h], table.rb[j], table.ln[j], seg_depth[s], L, &more);
         if (!more && depth < seg_cur[s]) seg_cur[s] = depth;
         if (more) long_list.push_back(static_cast<uint32_t>(a));
       }
@@ -224,12 +201,12 @@ extern "C" long so_sort(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
       for (uint32_t a : long_list) {
         const uint32_t s = sort::seg_of(list[a].seg_row);
         const uint32_t j = sort::row_of(list[a].seg_row), h = sort::row_of(list[seg_head[s]].seg_row);
-        const uint64_t both = rows.ln[h] < rows.ln[j] ? rows.ln[h] : rows.ln[j];
+        const uint64_t both = table.ln[h] < table.ln[j] ? table.ln[h] : table.ln[j];
         uint64_t depth = both;
         for (uint64_t d0 = seg_depth[s] + L; d0 < both && depth == both; d0 += 64 * sort::kGroupBytes) {
           uint64_t found = sort::kNoDepth;
           for (uint64_t lane = 0; lane < 64; lane++) {
-            const uint64_t at = sort::wave_group(T, n, rows.rb[h], rows.rb[j], both, d0, lane);
+            const uint64_t at = sort::wave_group(T, n, table.rb[h], table.rb[j], both, d0, lane);
             if (at == sort::kNoDepth) continue;
             if (found == sort::kNoDepth) found = at;
             else if (at <= found) return summary[6] = 6, -3;
@@ -242,15 +219,15 @@ extern "C" long so_sort(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
       for (uint64_t a = 0; a < n_active; a++) {
         const uint32_t s = sort::seg_of(list[a].seg_row);
         const uint32_t j = sort::row_of(list[a].seg_row), h = sort::row_of(list[seg_head[s]].seg_row);
-        if (seg_cur[s] < seg_depth[s] || seg_cur[s] > rows.ln[j] || memcmp(text + rows.rb[h], text + rows.rb[j], seg_cur[s]) != 0) return summary[6] = 1, -3;
+        if (seg_cur[s] < seg_depth[s] || seg_cur[s] > table.ln[j] || memcmp(text + table.rb[h], text + table.rb[j], seg_cur[s]) != 0) return summary[6] = 1, -3;
       }
     }
     // ---- key
     for (uint64_t a = 0; a < n_active; a++) {
       const uint32_t j = sort::row_of(list[a].seg_row);
       const uint64_t d = seg_cur[sort::seg_of(list[a].seg_row)];
-      if (d > rows.ln[j]) return -1;
-      list[a].key = sort::key(T, n, rows.rb[j], rows.ln[j], d);
+      if (d > table.ln[j]) return -1;
+      list[a].key = sort::key(T, n, table.rb[j], table.ln[j], d);
     }
     summary[2] += n_active;
     // ---- order: stable by key, then stable by the bits of the segment number
@@ -279,7 +256,7 @@ extern "C" long so_sort(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
     if (skips)
       for (uint64_t s = 0; s < n_segments; s++)
         if (parts[s] < 2 && still_open[s]) return summary[6] = 3, -3;
-    if (!equal_rows_ascend(rows, mem, k)) return summary[6] = 4, -3;
+    if (!equal_rows_ascend(table, mem, k)) return summary[6] = 4, -3;
     if (!skip && summary[0] > max_len / sort::kWindow + 1) return summary[6] = 2, -3;
     if (skip && summary[0] > distinct + 1) return summary[6] = 3, -3;
     n_active = open_rows, n_segments = open_segments;
@@ -297,12 +274,6 @@ extern "C" long so_sort(const uint8_t* text, uint64_t n, const uint64_t* rec_beg
 #include <stdio.h>
 
 namespace {
-
-uint64_t g_rng = 88172645463325252ull;
-uint64_t rnd(uint64_t below) {
-  g_rng ^= g_rng << 13, g_rng ^= g_rng >> 7, g_rng ^= g_rng << 17;
-  return g_rng % below;
-}
 
 // one case: k rows over a small alphabet behind a shared prefix, lengths around the window and the group, some rows a
 // prefix of their neighbour or differing in the last byte, laid out with 0..3 bytes between them, the last one ending at n

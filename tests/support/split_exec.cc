@@ -12,12 +12,13 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_split.h"
+#include "checked_table.h"
 
 using namespace rejit_amd;
 
 namespace {
 
-struct CheckedMem {
+struct CheckedSpans {
   const uint64_t *rb, *re, *first_;
   const uint32_t* counts;
   uint64_t n_records;
@@ -57,7 +58,7 @@ extern "C" long sp_split(uint64_t n, const uint64_t* rec_begin, const uint64_t* 
   summary[1] = ~0ull;
   const uint64_t k = have_indices ? n_indices : n_records;
   if (!split::sums_fit(k, m) || (what != split::kBetween && what != split::kMatches) || unit == 0 || chunk == 0) return -2;
-  const CheckedMem M{rec_begin, rec_end, first, counts, n_records, indices, n_indices, spans, m};
+  const CheckedSpans M{rec_begin, rec_end, first, counts, n_records, indices, n_indices, spans, m};
   // ---- plan: k + 1 rows, row k the closing one
   std::vector<uint64_t> own_first(k + 1);
   uint64_t* pf = piece_first ? piece_first : own_first.data();
@@ -132,12 +133,6 @@ extern "C" int sp_sums_fit(uint64_t k, uint64_t m) { return split::sums_fit(k, m
 #include <stdio.h>
 
 namespace {
-
-uint64_t g_rng = 88172645463325252ull;
-uint64_t rnd(uint64_t below) {
-  g_rng ^= g_rng << 13, g_rng ^= g_rng >> 7, g_rng ^= g_rng << 17;
-  return g_rng % below;
-}
 
 // one case: records of the given sizes (a seam of 2 text bytes between them), matches planted inside the records, the pieces
 // row by row from the meaning

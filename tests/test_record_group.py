@@ -8,19 +8,14 @@ The expectation is a Python dict over the rows' bytes, in insertion order:
     group[j] = the number of row j's string, rep[g] = the first j with string g, count[g] = how many rows have it.
 All comparisons are exact."""
 import ctypes
-import os
 import random
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
-SO = os.path.join(HERE, "support", "libgroup_exec.so")
-EXE = os.path.join(HERE, "support", "group_exec_asan")
-SRCS = [os.path.join(HERE, "support", "group_exec.cc")]
-DEPS = SRCS + [os.path.join(CSRC, h) for h in ("record_group.h", "record_pack.h")]
+from exec_build import _arr, headers, sanitized_program, shared_driver
+
+DEPS = headers(("record_group.h", "record_rows.h", "record_pack.h"), ("checked_text.h", "checked_table.h"))
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 NONE = (1 << 64) - 1
 POISON = 0xA5A5A5A5A5A5A5A5
@@ -28,15 +23,9 @@ BITS = (0, 1, 4, 64)
 UNITS = (1, 3, 256)
 
 
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in DEPS)
-
-
 @pytest.fixture(scope="module")
 def gx():
-    if _stale(SO):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", "-o", SO] + SRCS)
-    lib = ctypes.CDLL(SO)
+    lib = shared_driver("group_exec", DEPS)
     u64, u32, cp = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_char_p
     lib.gr_hash.restype = ctypes.c_long
     lib.gr_hash.argtypes = [cp, u64, u64, u64, u64, ctypes.c_int, u32, _u64p]
@@ -50,10 +39,6 @@ def gx():
     lib.gr_group.restype = ctypes.c_long
     lib.gr_group.argtypes = [cp, u64, _u64p, _u64p, u64, _u64p, ctypes.c_int, u64, u32, _u64p, u64, _u64p, _u64p, _u64p, u64, _u64p]
     return lib
-
-
-def _arr(xs):
-    return (ctypes.c_uint64 * max(len(xs), 1))(*xs)
 
 
 def hash_of(lib, text, begin, ln, lanes=1, blocked=0, bits=64):
@@ -334,9 +319,6 @@ def test_the_driver_is_clean_under_the_address_and_undefined_sanitizers():
     """The same driver as a stand-alone program with its own main(), built with -fsanitize=address,undefined and run as a
     child process: a fixed set of cases against a std::map, exact allocations.  (The sanitizers' runtimes are linked
     statically: nothing is preloaded, and nothing is loaded into Python.)"""
-    if _stale(EXE):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-static-libasan", "-static-libubsan", "-DGROUP_EXEC_MAIN", "-o", EXE] + SRCS)
-    r = subprocess.run([EXE], capture_output=True, timeout=300)
+    r = subprocess.run([sanitized_program("group_exec", DEPS)], capture_output=True, timeout=300)
     assert r.returncode == 0, (r.stdout.decode()[-400:], r.stderr.decode()[-2000:])
     assert b"192 cases" in r.stdout

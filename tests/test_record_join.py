@@ -7,18 +7,13 @@ expectation is a brute-force attribution in Python, straight from the rule's tex
 record i with rec_begin[i] <= b, and is kept iff b <= rec_end[i]; a kept match whose end lies beyond rec_end[i] crosses.
 Tiles of 1 .. 300 records; a staging capacity of 0, 1 and 7 begins forces the search in the list itself."""
 import ctypes
-import os
 import random
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
-SO = os.path.join(HERE, "support", "librecord_exec.so")
-SRCS = [os.path.join(HERE, "support", "record_exec.cc")]
-DEPS = SRCS + [os.path.join(CSRC, "record_join.h")]
+from exec_build import headers, shared_driver
+
+DEPS = headers(("record_join.h",))
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 NONE = (1 << 64) - 1
@@ -28,9 +23,7 @@ CAPS = (0, 1, 7, 4096)
 
 @pytest.fixture(scope="module")
 def rx():
-    if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(s) for s in DEPS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", "-o", SO] + SRCS)
-    lib = ctypes.CDLL(SO)
+    lib = shared_driver("record_exec", DEPS)
     lib.re_join.restype = ctypes.c_long
     lib.re_join.argtypes = [_u64p, ctypes.c_uint64, _u64p, _u64p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                             _u32p, _u64p, _u64p]

@@ -9,19 +9,14 @@ write to the table behind the build an error.  The expectation is a Python dict 
     index[j] = the first set row with probe row j's string, or NONE;  hits[i] = the probe rows that found set row i.
 The answer must be the same for every insert order, probe order, unit size and number of hash bits.  All comparisons are exact."""
 import ctypes
-import os
 import random
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
-SO = os.path.join(HERE, "support", "liblookup_exec.so")
-EXE = os.path.join(HERE, "support", "lookup_exec_asan")
-SRCS = [os.path.join(HERE, "support", "lookup_exec.cc")]
-DEPS = SRCS + [os.path.join(CSRC, h) for h in ("record_lookup.h", "record_group.h", "record_pack.h")]
+from exec_build import _arr, headers, sanitized_program, shared_driver
+
+DEPS = headers(("record_lookup.h", "record_group.h", "record_rows.h", "record_pack.h"), ("checked_text.h", "checked_table.h"))
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 NONE = (1 << 64) - 1
 POISON = 0xA5A5A5A5A5A5A5A5
@@ -31,15 +26,9 @@ UNITS = (1, 3, 64, 256)
 LENGTHS = (0, 1, 15, 16, 17, 31, 32, 33)
 
 
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in DEPS)
-
-
 @pytest.fixture(scope="module")
 def lx():
-    if _stale(SO):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", "-o", SO] + SRCS)
-    lib = ctypes.CDLL(SO)
+    lib = shared_driver("lookup_exec", DEPS)
     u64, u32, cp, ci = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_int
     lib.lk_rows_fit.argtypes = [u64, u64]
     lib.lk_layout.restype = None
@@ -50,10 +39,6 @@ def lx():
     lib.lk_lookup.argtypes = [cp, u64, _u64p, _u64p, u64, _u64p, ci, u64, cp, u64, _u64p, _u64p, u64, _u64p, ci, u64, u32, _u64p, _u64p, u64, ci, ci,
                               _u64p, _u64p, _u64p]
     return lib
-
-
-def _arr(xs):
-    return (ctypes.c_uint64 * max(len(xs), 1))(*xs)
 
 
 class Table:
@@ -350,9 +335,6 @@ def test_the_driver_is_clean_under_the_address_and_undefined_sanitizers():
     """The same driver as a stand-alone program with its own main(), built with -fsanitize=address,undefined and run as a
     child process: 192 seeded random cases against a std::map, two texts or one, exact allocations.  (The sanitizers' runtimes
     are linked statically: nothing is preloaded, and nothing is loaded into Python.)"""
-    if _stale(EXE):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-static-libasan", "-static-libubsan", "-DLOOKUP_EXEC_MAIN", "-o", EXE] + SRCS)
-    r = subprocess.run([EXE], capture_output=True, timeout=300)
+    r = subprocess.run([sanitized_program("lookup_exec", DEPS)], capture_output=True, timeout=300)
     assert r.returncode == 0, (r.stdout.decode()[-400:], r.stderr.decode()[-2000:])
     assert b"192 cases" in r.stdout

@@ -8,18 +8,13 @@ every 16-byte group searches the table).  The expectation is a brute-force pack 
 Chunks of 16, 48 and 4096 bytes, a stage of 0, 1, 7 and 1024 rows, units of 1, 3 and 256 rows.  The output and the tables are
 poisoned first: every byte of [0, min(total, out_cap)) and every row is written, nothing behind it is touched."""
 import ctypes
-import os
 import random
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
-SO = os.path.join(HERE, "support", "libpack_exec.so")
-SRCS = [os.path.join(HERE, "support", "pack_exec.cc")]
-DEPS = SRCS + [os.path.join(HERE, "support", "checked_text.h"), os.path.join(CSRC, "record_pack.h")]
+from exec_build import _arr, headers, shared_driver
+
+DEPS = headers(("record_pack.h",), ("checked_text.h",))
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 NONE = (1 << 64) - 1
@@ -32,9 +27,7 @@ FILL = 0x7C
 
 @pytest.fixture(scope="module")
 def px():
-    if not os.path.exists(SO) or any(os.path.getmtime(SO) < os.path.getmtime(s) for s in DEPS):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", "-o", SO] + SRCS)
-    lib = ctypes.CDLL(SO)
+    lib = shared_driver("pack_exec", DEPS)
     u64 = ctypes.c_uint64
     lib.pe_pack.restype = ctypes.c_long
     lib.pe_pack.argtypes = [ctypes.c_char_p, u64, _u64p, _u64p, u64, _u64p, u64, ctypes.c_uint32, u64, u64, u64, u64, u64, _u8p, u64, u64, u64,
@@ -43,10 +36,6 @@ def px():
     lib.pe_synth.argtypes = [u64]
     lib.pe_sums_fit.argtypes = [u64, u64, u64, u64]
     return lib
-
-
-def _arr(xs):
-    return (ctypes.c_uint64 * max(len(xs), 1))(*xs)
 
 
 def run(lib, text, n, records, indices, lead, gap, unit, chunk, cap, out_cap=None, tables=True, window=None, fill=FILL):

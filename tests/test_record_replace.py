@@ -11,22 +11,16 @@ counts / first come from the join rule of record_join.h written out in Python.  
 bytes, a stage of 0, 1, 7 and 1024 rows; the output and the tables are poisoned with 0xA5 first."""
 import bisect
 import ctypes
-import os
 import random
 import subprocess
 
 import pytest
 
 import test_record_pack as the_pack
+from exec_build import _arr, headers, sanitized_program, shared_driver
 from test_record_pack import px  # noqa: F401  (the fixture: the pack's driver, pack_exec.cc)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
-SO = os.path.join(HERE, "support", "libreplace_exec.so")
-EXE = os.path.join(HERE, "support", "replace_exec_asan")
-SRCS = [os.path.join(HERE, "support", "replace_exec.cc")]
-DEPS = SRCS + [os.path.join(HERE, "support", "checked_text.h"), os.path.join(CSRC, "record_replace.h"), os.path.join(CSRC, "record_pack.h")]
+DEPS = headers(("record_replace.h", "record_pack.h"), ("checked_text.h", "checked_table.h"))
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -41,25 +35,15 @@ FILL = 0x7C
 OK, BAD_INDEX, BAD_ROW, SATURATED, BAD_RANGE, BEGINS_BEFORE, CROSSES = range(7)      # replace::Kind
 
 
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in DEPS)
-
-
 @pytest.fixture(scope="module")
 def rx():
-    if _stale(SO):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", "-o", SO] + SRCS)
-    lib = ctypes.CDLL(SO)
+    lib = shared_driver("replace_exec", DEPS)
     u64 = ctypes.c_uint64
     lib.re_replace.restype = ctypes.c_long
     lib.re_replace.argtypes = [ctypes.c_char_p, u64, _u64p, _u64p, u64, _u32p, _u64p, _u64p, u64, _u64p, ctypes.c_int, u64, ctypes.c_char_p, u64,
                                ctypes.c_uint32, u64, u64, u64, u64, u64, u64, _u8p, u64, _u64p, _u64p, _u64p]
     lib.re_sums_fit.argtypes = [u64] * 6
     return lib
-
-
-def _arr(xs, ty=ctypes.c_uint64):
-    return (ty * max(len(xs), 1))(*xs)
 
 
 def join(records, spans):
@@ -393,9 +377,6 @@ def test_the_driver_is_clean_under_the_address_and_undefined_sanitizers():
     """The same driver as a stand-alone program with its own main(), built with -fsanitize=address,undefined and run as a
     child process: a fixed set of cases against a splice written out in C++, exact allocations.  (The sanitizers' runtimes are
     linked statically: nothing is preloaded, and nothing is loaded into Python.)"""
-    if _stale(EXE):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-static-libasan", "-static-libubsan", "-DREPLACE_EXEC_MAIN", "-o", EXE] + SRCS)
-    r = subprocess.run([EXE], capture_output=True, timeout=300)
+    r = subprocess.run([sanitized_program("replace_exec", DEPS)], capture_output=True, timeout=300)
     assert r.returncode == 0, (r.stdout.decode()[-400:], r.stderr.decode()[-2000:])
     assert b"216 cases" in r.stdout

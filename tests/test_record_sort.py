@@ -8,19 +8,14 @@ loop for every table (it returns -3 and says which one broke).  The expectation 
     sorted(range(k), key=lambda j: (rows[j], j))
 All comparisons are exact."""
 import ctypes
-import os
 import random
 import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
-SO = os.path.join(HERE, "support", "libsort_exec.so")
-EXE = os.path.join(HERE, "support", "sort_exec_asan")
-SRCS = [os.path.join(HERE, "support", "sort_exec.cc")]
-DEPS = SRCS + [os.path.join(CSRC, h) for h in ("record_sort.h", "record_pack.h")]
+from exec_build import _arr, headers, sanitized_program, shared_driver
+
+DEPS = headers(("record_sort.h", "record_rows.h", "record_pack.h"), ("checked_text.h", "checked_table.h"))
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 NONE = (1 << 64) - 1
 POISON = 0xA5A5A5A5A5A5A5A5
@@ -31,15 +26,9 @@ LENGTHS = (0, 1, 6, 7, 8, 13, 14, 15, 21, 63, 64, 65, 70)
 ALPHABETS = (bytes([0, 1]), b"ab", bytes([0, 0x80, 0xFF]) + b"a", bytes(range(256)))
 
 
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in DEPS)
-
-
 @pytest.fixture(scope="module")
 def sx():
-    if _stale(SO):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", "-o", SO] + SRCS)
-    lib = ctypes.CDLL(SO)
+    lib = shared_driver("sort_exec", DEPS)
     u64, u32, cp = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_char_p
     lib.so_key.restype = ctypes.c_long
     lib.so_key.argtypes = [cp, u64, u64, u64, u64, _u64p]
@@ -53,10 +42,6 @@ def sx():
     lib.so_sort.restype = ctypes.c_long
     lib.so_sort.argtypes = [cp, u64, _u64p, _u64p, u64, _u64p, ctypes.c_int, u64, u64, u32, ctypes.c_int, _u64p, _u64p]
     return lib
-
-
-def _arr(xs):
-    return (ctypes.c_uint64 * max(len(xs), 1))(*xs)
 
 
 def key_of(lib, text, begin, ln, d=0):
@@ -309,9 +294,6 @@ def test_the_driver_is_clean_under_the_address_and_undefined_sanitizers():
     """The same driver as a stand-alone program with its own main(), built with -fsanitize=address,undefined and run as a
     child process: a fixed set of cases with exact allocations, P1..P4 asserted inside.  (The sanitizers' runtimes are linked
     statically: nothing is preloaded, and nothing is loaded into Python.)"""
-    if _stale(EXE):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-static-libasan", "-static-libubsan", "-DSORT_EXEC_MAIN", "-o", EXE] + SRCS)
-    r = subprocess.run([EXE], capture_output=True, timeout=300)
+    r = subprocess.run([sanitized_program("sort_exec", DEPS)], capture_output=True, timeout=300)
     assert r.returncode == 0, (r.stdout.decode()[-400:], r.stderr.decode()[-2000:])
     assert b"270 cases" in r.stdout

@@ -10,21 +10,15 @@ most once.  The expectation is the meaning written out literally in Python, a lo
 counts / first come from the join rule of record_join.h written out in Python (test_record_replace.join).  Units of 1, 3 and
 256 rows, chunks of 1, 3, 16 and 4096 pieces, a stage of 0, 1, 7 and 1024 rows; the tables are poisoned with 0xA5 first."""
 import ctypes
-import os
 import random
 import subprocess
 
 import pytest
 
+from exec_build import _arr, headers, sanitized_program, shared_driver
 from test_record_replace import RECORDS, SPANS, join, splice
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "rejit_amd", "csrc")
-SO = os.path.join(HERE, "support", "libsplit_exec.so")
-EXE = os.path.join(HERE, "support", "split_exec_asan")
-SRCS = [os.path.join(HERE, "support", "split_exec.cc")]
-DEPS = SRCS + [os.path.join(CSRC, h) for h in ("record_split.h", "record_replace.h", "record_pack.h")]
+DEPS = headers(("record_split.h", "record_replace.h", "record_pack.h"), ("checked_table.h",))
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 NONE = (1 << 64) - 1
@@ -37,25 +31,15 @@ BETWEEN, MATCHES = 0, 1
 OK, BAD_INDEX, BAD_ROW, SATURATED, BAD_RANGE, BEGINS_BEFORE, CROSSES = range(7)      # replace::Kind
 
 
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(s) for s in DEPS)
-
-
 @pytest.fixture(scope="module")
 def sx():
-    if _stale(SO):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-fPIC", "-shared", "-o", SO] + SRCS)
-    lib = ctypes.CDLL(SO)
+    lib = shared_driver("split_exec", DEPS)
     u64 = ctypes.c_uint64
     lib.sp_split.restype = ctypes.c_long
     lib.sp_split.argtypes = [u64, _u64p, _u64p, u64, _u32p, _u64p, _u64p, u64, _u64p, ctypes.c_int, u64, ctypes.c_int, u64, u64, u64, _u64p, _u64p, _u64p,
                              u64, _u64p]
     lib.sp_sums_fit.argtypes = [u64, u64]
     return lib
-
-
-def _arr(xs, ty=ctypes.c_uint64):
-    return (ty * max(len(xs), 1))(*xs)
 
 
 def pieces_of(rb, re_, own, what):
@@ -322,9 +306,6 @@ def test_the_driver_is_clean_under_the_address_and_undefined_sanitizers():
     """The same driver as a stand-alone program with its own main(), built with -fsanitize=address,undefined and run as a
     child process: a fixed set of cases against the meaning written out in C++, exact allocations.  (The sanitizers' runtimes
     are linked statically: nothing is preloaded, and nothing is loaded into Python.)"""
-    if _stale(EXE):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-static-libasan", "-static-libubsan", "-DSPLIT_EXEC_MAIN", "-o", EXE] + SRCS)
-    r = subprocess.run([EXE], capture_output=True, timeout=300)
+    r = subprocess.run([sanitized_program("split_exec", DEPS)], capture_output=True, timeout=300)
     assert r.returncode == 0, (r.stdout.decode()[-400:], r.stderr.decode()[-2000:])
     assert b"96 cases" in r.stdout
