@@ -424,6 +424,46 @@ int64_t rj_scan_records_lookup(rj_scan* scan, const void* d_set_text, uint64_t s
                                const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
                                uint64_t* d_index, uint64_t* d_set_hits /* may be NULL */,
                                rj_lookup_stats* stats /* may be NULL */, void* hip_stream);
+/* The rows of a record table read AS NUMBERS (rejit_amd/csrc/record_parse.hip): `awk '{s[$1] += $3}'`,
+ * `awk '$9 >= 500'`, `sort -n`, Arrow's cast(utf8 -> int64 / uint64 / float64) -- exactly, or not at all, without a download.
+ * The row rules are those of rj_scan_records_pack / rj_scan_records_group: any order, repeats allowed through the index list, a
+ * non-NULL index list with count 0 is no rows; k is the number of rows, row j is text[rec_begin[r(j)], rec_end[r(j)]).
+ *     d_value[j]  = the row's int64, its uint64, or the IEEE-754 bits of its double; 0 when the status is not OK   (k uint64)
+ *     d_status[j] = RJ_PARSE_OK, or why the row has no value                                          (k bytes, may be NULL)
+ * D is [0-9].  With RJ_PARSE_TRIM the ASCII spaces and tabs before and behind the number are dropped first; without it they
+ * are ordinary bytes.  Nothing else is skipped: no underscores, no locale, no inf / nan / hex; a NUL is an ordinary byte.  The
+ * statuses, decided in this order:
+ *     RJ_PARSE_EMPTY      no bytes are left
+ *     RJ_PARSE_MALFORMED  the bytes are not in the kind's grammar: INT64 [+-]?D+, UINT64 \+?D+ (a `-` is malformed, `-0`
+ *                         included), FLOAT64 [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D+)?
+ *     RJ_PARSE_RANGE      integer kinds: the value is outside [-2^63, 2^63 - 1] / [0, 2^64 - 1] (leading zeros do not count)
+ *     RJ_PARSE_INEXACT    FLOAT64: with the row's exact decimal value written as +-m x 10^q, m not divisible by 10 -- a property
+ *                         of the value, not of its spelling: 1.50, 15e-1 and 0.0015e3 are (15, -1) --, the row is OK when m = 0
+ *                         (+-0.0 whatever the exponent says) or when m <= 2^53 and -22 <= q <= 22; everything else is INEXACT
+ * An OK value is what Python's int() / float() and strtod make of the row, bit for bit: inside the window double(m) and 10^|q|
+ * are exact and the value is one IEEE multiplication or division of the two, hence correctly rounded.  A row never gets a
+ * nearby value.  A later version may widen the window; it will never yield a value that is not the correctly rounded one.
+ * Returns n_ok.  Every row of d_value, and of d_status when given, is written exactly once, nothing has to be cleared first,
+ * nothing behind k is touched; k == 0 returns 0.  `stats` (may be NULL) receives the five counts; they add up to k.  A row of
+ * any length is legal (one lane walks it).  The scan lends scratch only: spans, stats and the state of its last rj_scan_records
+ * (rj_scan_records_select included) stay as they were.  One synchronise per call.
+ * Refusals (RJ_BAD_ARGUMENT; a refused call writes no output row and is never led outside the text or a table): an index >=
+ * n_records; a row without begin <= end <= n -- the message names the first bad row, "row <j> " --; a null argument (d_text
+ * with n > 0, the tables with n_records > 0, d_value with k > 0); a table or d_value that is not 8-byte aligned; an unknown
+ * kind, or a flag bit other than RJ_PARSE_TRIM.  An output that overlaps an input is undefined, as elsewhere in the family.
+ * k >= 2^31: RJ_TOO_LARGE, as in the rest of the family's row calls. */
+#define RJ_PARSE_INT64 0
+#define RJ_PARSE_UINT64 1
+#define RJ_PARSE_FLOAT64 2
+#define RJ_PARSE_TRIM 1u /* flags: ASCII space (0x20) and tab (0x09) before and behind the number are skipped */
+enum { RJ_PARSE_OK = 0, RJ_PARSE_EMPTY = 1, RJ_PARSE_MALFORMED = 2, RJ_PARSE_RANGE = 3, RJ_PARSE_INEXACT = 4 };
+typedef struct {
+  uint64_t n_ok, n_empty, n_malformed, n_range, n_inexact;
+} rj_parse_stats;
+int64_t rj_scan_records_parse(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                              const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
+                              int kind, unsigned flags, uint64_t* d_value, uint8_t* d_status /* may be NULL */,
+                              rj_parse_stats* stats /* may be NULL */, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

@@ -6,6 +6,7 @@ tests and bench.py.  There is no Python or CPU implementation of the matching pa
 library is missing, or no HIP device is present, every call fails loudly.
 """
 from .api import (RejitError, Program, Scan, MultiScan, build, library_path, load_library, device_count, stream_read_probe)  # noqa: F401
+from .api import PARSE_OK, PARSE_EMPTY, PARSE_MALFORMED, PARSE_RANGE, PARSE_INEXACT  # noqa: F401  (Scan.parse_records: a row's status)
 
 # (Round 6: the VALU lane-operations per text byte that bench.py's roofline_valu quotes are no longer constants typed in here
 # -- they went stale with every kernel edit -- but read from profiles/pmc_traffic.json, where tools/collect_profiles.py puts

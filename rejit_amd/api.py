@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -169,6 +169,15 @@ class _LookupStats(ctypes.Structure):
     _fields_ = [("n_found", ctypes.c_uint64), ("n_set_distinct", ctypes.c_uint64), ("n_set_hit", ctypes.c_uint64), ("long_rows", ctypes.c_uint64)]
 
 
+class _ParseStats(ctypes.Structure):
+    _fields_ = [("n_ok", ctypes.c_uint64), ("n_empty", ctypes.c_uint64), ("n_malformed", ctypes.c_uint64), ("n_range", ctypes.c_uint64),
+                ("n_inexact", ctypes.c_uint64)]
+
+
+PARSE_KINDS = {"int64": 0, "uint64": 1, "float64": 2}                      # RJ_PARSE_INT64, _UINT64, _FLOAT64
+PARSE_OK, PARSE_EMPTY, PARSE_MALFORMED, PARSE_RANGE, PARSE_INEXACT = range(5)   # a row's status (RJ_PARSE_OK, ...)
+
+
 class RecordsResult:
     """What Scan.run_records returns: rj_record_stats (n_kept, n_matching, n_crossing, n_matches) and the per-record tensors --
     counts (int32: the library's uint32, saturating, so 2^32 - 1 reads -1) and first (int64), both on the text's device.
@@ -203,7 +212,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse"]
 
 
 def load_library():
@@ -317,6 +326,8 @@ def load_library():
     L.rj_scan_records_sort.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, ctypes.POINTER(_SortStats), vp]
     L.rj_scan_records_lookup.restype = i64
     L.rj_scan_records_lookup.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, vp, ctypes.POINTER(_LookupStats), vp]
+    L.rj_scan_records_parse.restype = i64
+    L.rj_scan_records_parse.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_uint, vp, vp, ctypes.POINTER(_ParseStats), vp]
     _lib = L
     return L
 
@@ -882,6 +893,45 @@ class Scan:
         if stats:
             answer += ({f: int(getattr(out, f)) for f, _ in _LookupStats._fields_},)
         return answer if len(answer) > 1 else index
+
+    def parse_records(self, text_tensor, rec_begin, rec_end, indices=None, kind="int64", trim=False, stats=False, stream=None):
+        """rj_scan_records_parse: the rows text[rec_begin[i], rec_end[i]) -- all of them, or those `indices` names, as
+        pack_records' -- read as numbers, exactly or not at all: Arrow's cast(utf8 -> int64 / uint64 / float64), the value
+        behind `awk '{s[$1] += $3}'` and `sort -n`.  kind is "int64", "uint64" or "float64"; trim=True drops the spaces and tabs
+        before and behind the number first.  Returns (values, status), device tensors of k entries: status (uint8) is
+        PARSE_OK, PARSE_EMPTY, PARSE_MALFORMED, PARSE_RANGE (the integer kinds) or PARSE_INEXACT ("float64": the value is
+        outside the window m <= 2^53, |q| <= 22 in which one IEEE operation gives float()'s bits); values holds what Python's
+        int() / float() make of an OK row, bit for bit, and 0 for every other row.  values is an int64 tensor for "int64", a
+        float64 tensor for "float64", and for "uint64" an int64 tensor that holds the value's 64 BITS (torch has no arithmetic
+        on uint64): a value >= 2^63 reads as value - 2^64.  With stats=True also {"n_ok", "n_empty", "n_malformed", "n_range",
+        "n_inexact"}.  (status == PARSE_OK) is the `ok` of records.group_sums.  RejitError (RJ_BAD_ARGUMENT, naming the first
+        bad row) for a bad index or row.  The scan's spans, stats and select_records stay as they were."""
+        import torch
+
+        t = text_tensor
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        if kind not in PARSE_KINDS:
+            raise ValueError("parse_records: kind is 'int64', 'uint64' or 'float64', not %r" % (kind,))
+        n_records = int(rec_begin.numel())
+        for x in (rec_begin, rec_end):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
+        else:
+            k = n_records
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        values = torch.empty(k, dtype=torch.float64 if kind == "float64" else torch.int64, device=t.device)
+        status = torch.empty(k, dtype=torch.uint8, device=t.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        out = _ParseStats()
+        _check(self._lib.rj_scan_records_parse(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k, PARSE_KINDS[kind],
+                                               1 if trim else 0, ptr(values), ptr(status), ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
+        if stats:
+            return values, status, {f: int(getattr(out, f)) for f, _ in _ParseStats._fields_}
+        return values, status
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""

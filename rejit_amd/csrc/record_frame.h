@@ -1,5 +1,5 @@
 // rejit_amd/csrc/record_frame.h -- what the record units (record_join.hip, record_pack.hip, record_replace.hip,
-// record_split.hip, record_group.hip with record_group_build.h, record_sort.hip, record_lookup.hip) share, in ONE place: the
+// record_split.hip, record_group.hip with record_group_build.h, record_sort.hip, record_lookup.hip, record_parse.hip) share, in ONE place: the
 // summary words of their calls and when they refuse one, the 64-bit wave sums, the first bad row and the list of flagged
 // rows as a wave leaves them, the 16-byte read of a device text at any alignment (record_rows.h's Text), the rows of a
 // record table, the unit of a persistent scan in arrival order (ticket, publish, resolve, timed-out), the plan over it, the

@@ -1,5 +1,6 @@
 // rejit_amd/csrc/record_rows.h -- what the calls that read the ROWS of a record table say about a row's bytes, in ONE place:
-// rj_scan_records_group (record_group.h), rj_scan_records_sort (record_sort.h) and rj_scan_records_lookup (record_lookup.h).
+// rj_scan_records_group (record_group.h), rj_scan_records_sort (record_sort.h), rj_scan_records_lookup (record_lookup.h) and
+// rj_scan_records_parse (record_parse.h).
 // The limits their scratches share, the row a call's j names (or that it names none), 16 bytes of a row at any place of the
 // text, a row as zero-padded 16-byte groups, and the equality of two rows group by group.  Host and device code: the CPU
 // tests drive exactly these functions (tests/support/) through a Text policy, as the kernels do.

@@ -145,3 +145,24 @@ def join_rows(index, set_group, set_count):
     within = torch.arange(probe_row.numel(), dtype=torch.int64, device=index.device) - torch.repeat_interleave(begin, counts)
     set_row = by_group[torch.repeat_interleave(first[groups], counts) + within]
     return probe_row.contiguous(), set_row.contiguous()
+
+
+def group_sums(group, values, ok, n_groups: int):
+    """The per-group sum of the OK rows' values: `awk '{s[$1] += $2}'` behind Scan.group_records (group: its `group`, n_groups:
+    the length of its `rep`) and Scan.parse_records (values; ok: status == PARSE_OK, a bool tensor) over the same rows.  A
+    tensor of n_groups entries of values' dtype on its device: int64 sums wrap as int64 does, float64 sums are added in
+    index_add_'s order of the rows (on a GPU that order is not fixed: the last bits may differ from run to run).  Rows that
+    are not ok add 0; a group without an ok row sums to 0 (group_counts_ok tells it from a sum of 0).  Torch only and
+    device-agnostic."""
+    import torch
+
+    sums = torch.zeros(int(n_groups), dtype=values.dtype, device=values.device)
+    return sums.index_add_(0, group, torch.where(ok, values, torch.zeros_like(values)))
+
+
+def group_counts_ok(group, ok, n_groups: int):
+    """The number of OK rows per group (int64, n_groups entries): the divisor of a mean, and what tells an empty sum from 0."""
+    import torch
+
+    counts = torch.zeros(int(n_groups), dtype=torch.int64, device=group.device)
+    return counts.index_add_(0, group, ok.to(torch.int64))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K]] [-b] [-k KEYS] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M]] [-b] [-k KEYS] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -23,6 +23,12 @@ answer on the GPU:
        occurrences in front as "%7d %s" (`... | sort | uniq -c` without the sort's order): rj_scan_records_group groups the pieces
        by their bytes on the device; only the packed dictionary and the counts come back
   -t K   with -u: only the K most frequent, by descending count, ties in order of first appearance (`| sort -rn | head -K`)
+  -a M   with -f N -u: behind each distinct value of field N also print the SUM of field M (1-based) over its lines, as
+       "%7d %s %d" (`awk -F PATTERN '{c[$N]++; s[$N] += $M} END {...}'`): rj_scan_records_parse reads field M of every line as an
+       int64 on the device (spaces and tabs around the number are dropped), records.group_sums adds the values per group; only
+       the dictionary, the counts and the sums come back.  NOT awk's numeric-prefix rule: awk reads "12abc" as 12, "1.9" as 1.9
+       and "1e3" as 1000; here a field adds its value only when ALL of it is an integer [+-]?[0-9]+ inside int64 -- a line whose
+       field M is missing, empty, "12abc", "1.9", "1e3" or out of range adds 0 --, and the sum wraps as int64 does
   -b   byte order (`LC_ALL=C sort`), made on the device by rj_scan_records_sort: with -u the distinct values print in the
        order of their bytes with their counts (`... | sort | uniq -c`; with -t K the K most frequent, ties in byte order);
        with -p, -o or -f N and no -u the selected lines, the matches or the fields print sorted (`... | sort`)
@@ -61,13 +67,18 @@ def main(argv):
     if "-k" in argv[:-1]:
         at = argv.index("-k")
         keys, argv = argv[at + 1], argv[:at] + argv[at + 2:]
+    agg = None
+    if "-a" in argv[:-1]:
+        at = argv.index("-a")
+        agg, argv = argv[at + 1], argv[:at] + argv[at + 2:]
     matches_out, unique, byte_order = "-o" in argv, "-u" in argv, "-b" in argv
     argv = [a for a in argv if a not in ("-o", "-u", "-b")]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
     if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)) or (top is not None and (not top.isdigit() or not unique)) or (
             unique and not matches_out and field is None) or (byte_order and not matches_out and field is None and "-p" not in flags) or (
-            keys is not None and (repl is not None or top is not None or matches_out or unique or byte_order)):
+            keys is not None and (repl is not None or top is not None or matches_out or unique or byte_order or agg is not None)) or (
+            agg is not None and (not agg.isdigit() or int(agg) < 1 or not unique or field is None or matches_out)):
         sys.stderr.write(__doc__)
         return 2
     path, pattern = rest
@@ -146,19 +157,29 @@ def main(argv):
             if matches_out:
                 keep = records.nonempty_pieces(pb, pe)
             else:
+                if agg is not None:
+                    ab, ae, _ = records.field_records(pb, pe, pf, int(agg) - 1)      # (a missing field is an empty record: RJ_PARSE_EMPTY)
                 pb, pe, _ = records.field_records(pb, pe, pf, int(field) - 1)
                 keep = None
             if unique and (keep is None or keep.numel()):
                 if byte_order:
-                    rep, count, _ = records.sorted_groups(scan, text, pb, pe, indices=keep)
+                    rep, count, group = records.sorted_groups(scan, text, pb, pe, indices=keep)
                 else:
-                    _, rep, count = scan.group_records(text, pb, pe, indices=keep)
+                    group, rep, count = scan.group_records(text, pb, pe, indices=keep)
+                sums = None
+                if agg is not None:
+                    values, status = scan.parse_records(text, ab, ae, kind="int64", trim=True)
+                    sums = records.group_sums(group, values, status == rejit_amd.PARSE_OK, int(rep.numel()))
                 if top is not None:
-                    count, rep, _ = records.top_groups(count, rep, int(top))
+                    count, rep, order = records.top_groups(count, rep, int(top))
+                    sums = None if sums is None else sums[order]
                 packed, _, _ = scan.pack_records(text, pb, pe, indices=rep if keep is None else keep[rep], fill=10, lead=0, gap=1)
                 words = packed.cpu().numpy().tobytes().split(b"\n")     # the dictionary and the counts: the only downloads
                 sys.stdout.flush()
-                sys.stdout.buffer.write(b"".join(b"%7d %s\n" % (c, w) for c, w in zip(count.cpu().tolist(), words)))
+                if sums is None:
+                    sys.stdout.buffer.write(b"".join(b"%7d %s\n" % (c, w) for c, w in zip(count.cpu().tolist(), words)))
+                else:
+                    sys.stdout.buffer.write(b"".join(b"%7d %s %d\n" % (c, w, a) for c, w, a in zip(count.cpu().tolist(), words, sums.cpu().tolist())))
             elif keep is None or keep.numel():
                 if byte_order:
                     order = scan.sort_records(text, pb, pe, indices=keep)
