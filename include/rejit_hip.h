@@ -436,13 +436,30 @@ int64_t rj_scan_records_lookup(rj_scan* scan, const void* d_set_text, uint64_t s
  *     RJ_PARSE_EMPTY      no bytes are left
  *     RJ_PARSE_MALFORMED  the bytes are not in the kind's grammar: INT64 [+-]?D+, UINT64 \+?D+ (a `-` is malformed, `-0`
  *                         included), FLOAT64 [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D+)?
- *     RJ_PARSE_RANGE      integer kinds: the value is outside [-2^63, 2^63 - 1] / [0, 2^64 - 1] (leading zeros do not count)
+ *     RJ_PARSE_RANGE      integer kinds: the value is outside [-2^63, 2^63 - 1] / [0, 2^64 - 1] (leading zeros do not count);
+ *                         FLOAT64 under RJ_PARSE_WIDE only (below): the correctly rounded double is infinite
  *     RJ_PARSE_INEXACT    FLOAT64: with the row's exact decimal value written as +-m x 10^q, m not divisible by 10 -- a property
  *                         of the value, not of its spelling: 1.50, 15e-1 and 0.0015e3 are (15, -1) --, the row is OK when m = 0
  *                         (+-0.0 whatever the exponent says) or when m <= 2^53 and -22 <= q <= 22; everything else is INEXACT
  * An OK value is what Python's int() / float() and strtod make of the row, bit for bit: inside the window double(m) and 10^|q|
  * are exact and the value is one IEEE multiplication or division of the two, hence correctly rounded.  A row never gets a
- * nearby value.  A later version may widen the window; it will never yield a value that is not the correctly rounded one.
+ * nearby value.
+ * With RJ_PARSE_WIDE (FLOAT64; accepted and without effect for the integer kinds, so one flags word serves every column) the
+ * window is widened to every decimal the walk can hold, by integer arithmetic (the Eisel-Lemire product over a table of 128-bit
+ * powers of five).  Grammar, TRIM, EMPTY and MALFORMED are as before.  Let S be the row's significant
+ * digits, from the first non-zero mantissa digit to the last, and the value int(S) x 10^q -- the (m, q) above:
+ *     no such digit          OK with +-0.0, as without the flag
+ *     int(S) <= 2^64 - 1     the row is decided: OK with the correctly rounded double -- float()'s bits; subnormals, and +-0.0 for
+ *                            1e-400, included --, or RJ_PARSE_RANGE (value 0) when that double is infinite: 1e309 and
+ *                            1.7976931348623159e308 are RANGE, 1.7976931348623158e308 is OK.  Every spelling with up to 19
+ *                            significant digits is decided, and many with 20.
+ *     otherwise              with P the longest prefix of S that fits 64 bits and r = len(S) - len(P), the value lies strictly
+ *                            between P x 10^(q + r) and (P + 1) x 10^(q + r): when both ends round to one double the row is OK with
+ *                            it (rounding is monotone); when both are infinite it is RANGE; when they differ, or P = 2^64 - 1, it
+ *                            is RJ_PARSE_INEXACT -- a property of the value, not of its spelling or of where the row is cut.
+ * So under RJ_PARSE_WIDE a FLOAT64 row can be RJ_PARSE_RANGE (n_range counts it), every row that is OK without the flag keeps its
+ * bits, and INEXACT is left to the few rows of more than 64 bits of mantissa whose bracket straddles a rounding boundary.
+ * Without the flag nothing changes.  A row still never gets a value that is not the correctly rounded one.
  * Returns n_ok.  Every row of d_value, and of d_status when given, is written exactly once, nothing has to be cleared first,
  * nothing behind k is touched; k == 0 returns 0.  `stats` (may be NULL) receives the five counts; they add up to k.  A row of
  * any length is legal (one lane walks it).  The scan lends scratch only: spans, stats and the state of its last rj_scan_records
@@ -450,12 +467,13 @@ int64_t rj_scan_records_lookup(rj_scan* scan, const void* d_set_text, uint64_t s
  * Refusals (RJ_BAD_ARGUMENT; a refused call writes no output row and is never led outside the text or a table): an index >=
  * n_records; a row without begin <= end <= n -- the message names the first bad row, "row <j> " --; a null argument (d_text
  * with n > 0, the tables with n_records > 0, d_value with k > 0); a table or d_value that is not 8-byte aligned; an unknown
- * kind, or a flag bit other than RJ_PARSE_TRIM.  An output that overlaps an input is undefined, as elsewhere in the family.
+ * kind, or a flag bit other than RJ_PARSE_TRIM and RJ_PARSE_WIDE.  An output that overlaps an input is undefined, as elsewhere in the family.
  * k >= 2^31: RJ_TOO_LARGE, as in the rest of the family's row calls. */
 #define RJ_PARSE_INT64 0
 #define RJ_PARSE_UINT64 1
 #define RJ_PARSE_FLOAT64 2
 #define RJ_PARSE_TRIM 1u /* flags: ASCII space (0x20) and tab (0x09) before and behind the number are skipped */
+#define RJ_PARSE_WIDE 4u /* flags: FLOAT64 rows outside the exact window get their correctly rounded double (above); 2u is reserved */
 enum { RJ_PARSE_OK = 0, RJ_PARSE_EMPTY = 1, RJ_PARSE_MALFORMED = 2, RJ_PARSE_RANGE = 3, RJ_PARSE_INEXACT = 4 };
 typedef struct {
   uint64_t n_ok, n_empty, n_malformed, n_range, n_inexact;

@@ -9,7 +9,7 @@ from typing import List, Optional, Tuple
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "pow5_table.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -175,6 +175,7 @@ class _ParseStats(ctypes.Structure):
 
 
 PARSE_KINDS = {"int64": 0, "uint64": 1, "float64": 2}                      # RJ_PARSE_INT64, _UINT64, _FLOAT64
+PARSE_TRIM, PARSE_WIDE = 1, 4                                              # flags (RJ_PARSE_TRIM, RJ_PARSE_WIDE; 2 is reserved)
 PARSE_OK, PARSE_EMPTY, PARSE_MALFORMED, PARSE_RANGE, PARSE_INEXACT = range(5)   # a row's status (RJ_PARSE_OK, ...)
 
 
@@ -894,7 +895,7 @@ class Scan:
             answer += ({f: int(getattr(out, f)) for f, _ in _LookupStats._fields_},)
         return answer if len(answer) > 1 else index
 
-    def parse_records(self, text_tensor, rec_begin, rec_end, indices=None, kind="int64", trim=False, stats=False, stream=None):
+    def parse_records(self, text_tensor, rec_begin, rec_end, indices=None, kind="int64", trim=False, stats=False, stream=None, wide=False):
         """rj_scan_records_parse: the rows text[rec_begin[i], rec_end[i]) -- all of them, or those `indices` names, as
         pack_records' -- read as numbers, exactly or not at all: Arrow's cast(utf8 -> int64 / uint64 / float64), the value
         behind `awk '{s[$1] += $3}'` and `sort -n`.  kind is "int64", "uint64" or "float64"; trim=True drops the spaces and tabs
@@ -905,7 +906,11 @@ class Scan:
         float64 tensor for "float64", and for "uint64" an int64 tensor that holds the value's 64 BITS (torch has no arithmetic
         on uint64): a value >= 2^63 reads as value - 2^64.  With stats=True also {"n_ok", "n_empty", "n_malformed", "n_range",
         "n_inexact"}.  (status == PARSE_OK) is the `ok` of records.group_sums.  RejitError (RJ_BAD_ARGUMENT, naming the first
-        bad row) for a bad index or row.  The scan's spans, stats and select_records stay as they were."""
+        bad row) for a bad index or row.  The scan's spans, stats and select_records stay as they were.
+        wide=True (RJ_PARSE_WIDE; without effect for the integer kinds) widens "float64" beyond that window: every row whose
+        significant digits fit 64 bits -- repr() of a double, %.17g, 1e23, 0.30000000000000004 -- is OK with float()'s bits, or
+        PARSE_RANGE when float() would give inf (so PARSE_RANGE can occur for "float64" under wide); a longer mantissa is OK when
+        the two 64-bit decimals that bracket it round to one double, and PARSE_INEXACT only when they do not."""
         import torch
 
         t = text_tensor
@@ -928,7 +933,7 @@ class Scan:
         ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
         out = _ParseStats()
         _check(self._lib.rj_scan_records_parse(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k, PARSE_KINDS[kind],
-                                               1 if trim else 0, ptr(values), ptr(status), ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
+                                               (PARSE_TRIM if trim else 0) | (PARSE_WIDE if wide else 0), ptr(values), ptr(status), ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
         if stats:
             return values, status, {f: int(getattr(out, f)) for f, _ in _ParseStats._fields_}
         return values, status

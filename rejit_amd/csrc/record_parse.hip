@@ -14,6 +14,10 @@
 //   with ballots into wave-uniform registers; at its end a wave adds its counts to the workgroup's (LDS), and the workgroup
 //   issues ONE atomic add per class that occurred -- a few thousand adds on a summary word per call, not one per 64 rows
 //   (156 250 adds on one address were the whole run time of 10^7 rows: profiles/parse_probe.txt).
+//   FLOAT64 under RJ_PARSE_WIDE has an instantiation of its own (kWide): the same walk with the wide state's digit rule, and a
+//   finish that gives the lanes outside Clinger's window their Eisel-Lemire product -- a count of leading zeros, one or two
+//   64 x 64 -> 128 products and two words of pow5_table.h's 10 KB table, fetched per lane through the vector caches.  The
+//   three kernels without the flag are compiled from the *_as<false> functions: the code they always had.
 // Nothing here waits for another lane's progress.  The rows, the text and the refusal are record_frame.h's.
 #include <hip/hip_runtime.h>
 
@@ -30,6 +34,9 @@ namespace {
 __device__ __forceinline__ uint32_t status_word(uint32_t status) { return status < kSumBadWord ? status : status + 1; }
 static_assert(kSumKept == 0 && kSumMatching == 1 && kSumCrossing == 2 && kSumBadWord == 3 && kSumSelected == 4 && kSumTotal == 5, "status_word");
 constexpr unsigned kParseGrid = 256 * 8;   // persistent: eight workgroups (a wave per SIMD each) for each of the 256 CUs
+// the wide instantiation needs 69 VGPRs, seven waves per SIMD (profiles/parse_wide_kernel_resources.txt): a grid of eight
+// workgroups per CU would leave every eighth one to run its whole share behind the others
+constexpr unsigned kParseWideGrid = 256 * 7;
 
 __global__ __launch_bounds__(kThreads) void record_parse_check_kernel(Rows R, uint64_t n_records, uint64_t n, uint64_t k, uint64_t n_units,
                                                                       unsigned long long* summary) {
@@ -40,7 +47,7 @@ __global__ __launch_bounds__(kThreads) void record_parse_check_kernel(Rows R, ui
   }
 }
 
-template <int kKind>
+template <int kKind, bool kWide>
 __global__ __launch_bounds__(kThreads) void record_parse_kernel(const uint8_t* __restrict__ text, uint64_t n, Rows R, uint64_t n_records, uint64_t k,
                                                                 uint64_t n_units, unsigned flags, uint64_t* __restrict__ value,
                                                                 uint8_t* __restrict__ status, unsigned long long* summary) {
@@ -58,17 +65,17 @@ __global__ __launch_bounds__(kThreads) void record_parse_kernel(const uint8_t* _
       numparse::Result res{numparse::kMalformed, 0};
       if (!row.bad) {   // (every row passed the check; a lane is still never led outside the text)
         const uint64_t len = row.len(), groups = rows::n_groups(len);
-        numparse::State s = numparse::start(kKind, flags);
+        numparse::State s = numparse::start_as<kWide>(kKind, flags);
         uint32_t w[4] = {0, 0, 0, 0};
         if (groups) rows::load_group(src, n, row.rb, len, 0, w);
         for (uint64_t g = 0; g < groups && !numparse::done(s); g++) {
           uint32_t next[4] = {0, 0, 0, 0};
           if (g + 1 < groups) rows::load_group(src, n, row.rb, len, g + 1, next);
           const uint64_t left = len - g * rows::kGroupBytes;
-          numparse::step(s, w, left < rows::kGroupBytes ? static_cast<uint32_t>(left) : static_cast<uint32_t>(rows::kGroupBytes));
+          numparse::step_as<kWide>(s, w, left < rows::kGroupBytes ? static_cast<uint32_t>(left) : static_cast<uint32_t>(rows::kGroupBytes));
           w[0] = next[0], w[1] = next[1], w[2] = next[2], w[3] = next[3];
         }
-        res = numparse::finish(s, kKind);
+        res = numparse::finish_as<kWide>(s, kKind);
       }
       st = res.status;
       value[j] = res.bits;
@@ -106,7 +113,7 @@ int64_t rj_scan_records_parse(rj_scan* s, const void* d_text, uint64_t n, const 
   if (!aligned8(d_rec_begin, d_rec_end, d_indices, d_value)) return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records_parse: a table is not 8-byte aligned");
   if (!numparse::kind_known(kind))
     return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records_parse: kind %d is not RJ_PARSE_INT64, RJ_PARSE_UINT64 or RJ_PARSE_FLOAT64", kind);
-  if (!numparse::flags_known(flags)) return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records_parse: flags %#x: the only flag is RJ_PARSE_TRIM", flags);
+  if (!numparse::flags_known(flags)) return rj_fail(RJ_BAD_ARGUMENT, "rj_scan_records_parse: flags %#x: the flags are RJ_PARSE_TRIM and RJ_PARSE_WIDE", flags);
   if (!rows::rows_fit(k))
     return rj_fail(RJ_TOO_LARGE, "rj_scan_records_parse: %llu rows: the record calls that read rows take fewer than 2^31 of them",
                    static_cast<unsigned long long>(k));
@@ -119,13 +126,16 @@ int64_t rj_scan_records_parse(rj_scan* s, const void* d_text, uint64_t n, const 
   if ((rc = records_begin(s, 0, st, &scratch, &summary)) != RJ_OK) return rc;
   const Rows R{d_rec_begin, d_rec_end, d_indices};
   const uint8_t* text = static_cast<const uint8_t*>(d_text);
+  const bool wide = kind == numparse::kFloat64 && (flags & numparse::kWideFlag);   // (RJ_PARSE_WIDE is inert for the integer kinds)
   const dim3 block(kThreads), grid(static_cast<unsigned>(n_units < kParseGrid ? n_units : kParseGrid));
+  const dim3 wide_grid(static_cast<unsigned>(n_units < kParseWideGrid ? n_units : kParseWideGrid));
   hipLaunchKernelGGL(record_parse_check_kernel, dim3(unit_grid(n_units)), block, 0, st, R, n_records, n, k, n_units, summary);
-#define RJ_PARSE_LAUNCH(KIND) \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(record_parse_kernel<KIND>), grid, block, 0, st, text, n, R, n_records, k, n_units, flags, d_value, d_status, summary)
-  if (kind == numparse::kInt64) RJ_PARSE_LAUNCH(numparse::kInt64);
-  else if (kind == numparse::kUint64) RJ_PARSE_LAUNCH(numparse::kUint64);
-  else RJ_PARSE_LAUNCH(numparse::kFloat64);
+#define RJ_PARSE_LAUNCH(KIND, WIDE) \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(record_parse_kernel<KIND, WIDE>), WIDE ? wide_grid : grid, block, 0, st, text, n, R, n_records, k, n_units, flags, d_value, d_status, summary)
+  if (kind == numparse::kInt64) RJ_PARSE_LAUNCH(numparse::kInt64, false);
+  else if (kind == numparse::kUint64) RJ_PARSE_LAUNCH(numparse::kUint64, false);
+  else if (wide) RJ_PARSE_LAUNCH(numparse::kFloat64, true);
+  else RJ_PARSE_LAUNCH(numparse::kFloat64, false);
 #undef RJ_PARSE_LAUNCH
   if ((rc = records_finish(s, kCall, st)) != RJ_OK) return rc;
   if (s->rec_host[kSumBadWord] != 0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M]] [-b] [-k KEYS] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -29,6 +29,11 @@ answer on the GPU:
        the dictionary, the counts and the sums come back.  NOT awk's numeric-prefix rule: awk reads "12abc" as 12, "1.9" as 1.9
        and "1e3" as 1000; here a field adds its value only when ALL of it is an integer [+-]?[0-9]+ inside int64 -- a line whose
        field M is missing, empty, "12abc", "1.9", "1e3" or out of range adds 0 --, and the sum wraps as int64 does
+  -A M   as -a M, but the sum is a float64, printed as Python's repr() writes it ("%7d %s %r"): field M is read as a double
+       with RJ_PARSE_TRIM | RJ_PARSE_WIDE -- [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D+)?, correctly rounded, so "1.9", "1e3" and
+       "0.30000000000000004" add their values --; a field that is missing, malformed, infinite as a double or (more than 64 bits
+       of mantissa, rarely) INEXACT adds 0.  The order in which a group's values are added is not fixed, as for any float sum on
+       the device.  Not together with -a
   -b   byte order (`LC_ALL=C sort`), made on the device by rj_scan_records_sort: with -u the distinct values print in the
        order of their bytes with their counts (`... | sort | uniq -c`; with -t K the K most frequent, ties in byte order);
        with -p, -o or -f N and no -u the selected lines, the matches or the fields print sorted (`... | sort`)
@@ -71,6 +76,10 @@ def main(argv):
     if "-a" in argv[:-1]:
         at = argv.index("-a")
         agg, argv = argv[at + 1], argv[:at] + argv[at + 2:]
+    agg_float = False
+    if "-A" in argv[:-1] and agg is None:
+        at = argv.index("-A")
+        agg, agg_float, argv = argv[at + 1], True, argv[:at] + argv[at + 2:]
     matches_out, unique, byte_order = "-o" in argv, "-u" in argv, "-b" in argv
     argv = [a for a in argv if a not in ("-o", "-u", "-b")]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
@@ -168,7 +177,7 @@ def main(argv):
                     group, rep, count = scan.group_records(text, pb, pe, indices=keep)
                 sums = None
                 if agg is not None:
-                    values, status = scan.parse_records(text, ab, ae, kind="int64", trim=True)
+                    values, status = scan.parse_records(text, ab, ae, kind="float64" if agg_float else "int64", trim=True, wide=agg_float)
                     sums = records.group_sums(group, values, status == rejit_amd.PARSE_OK, int(rep.numel()))
                 if top is not None:
                     count, rep, order = records.top_groups(count, rep, int(top))
@@ -178,6 +187,8 @@ def main(argv):
                 sys.stdout.flush()
                 if sums is None:
                     sys.stdout.buffer.write(b"".join(b"%7d %s\n" % (c, w) for c, w in zip(count.cpu().tolist(), words)))
+                elif agg_float:
+                    sys.stdout.buffer.write(b"".join(b"%7d %s %s\n" % (c, w, repr(a).encode()) for c, w, a in zip(count.cpu().tolist(), words, sums.cpu().tolist())))
                 else:
                     sys.stdout.buffer.write(b"".join(b"%7d %s %d\n" % (c, w, a) for c, w, a in zip(count.cpu().tolist(), words, sums.cpu().tolist())))
             elif keep is None or keep.numel():
