@@ -482,6 +482,48 @@ int64_t rj_scan_records_parse(rj_scan* scan, const void* d_text, uint64_t n, con
                               const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
                               int kind, unsigned flags, uint64_t* d_value, uint8_t* d_status /* may be NULL */,
                               rj_parse_stats* stats /* may be NULL */, void* hip_stream);
+/* A column of numbers written AS DECIMAL TEXT (rejit_amd/csrc/record_format.hip): the inverse of
+ * rj_scan_records_parse -- the sums of an aggregation, line numbers, Arrow's cast(int64 / uint64 / float64 -> utf8) -- as a new
+ * device text and its record table, without a download.  d_value: n_values 64-bit words, read by `kind` (the kind numbers of
+ * RJ_PARSE_*): an int64, a uint64, or the IEEE-754 bits of a double.  With k = d_indices ? n_indices : n_values and
+ * r(j) = d_indices ? d_indices[j] : j (a take, a permutation, the order of a top-K; repeats allowed; a non-NULL list with count 0
+ * is no rows), row j's bytes T(j) are made from d_value[r(j)], and the layout is rj_scan_records_pack's with len(j) = |T(j)|:
+ *     ob(0) = lead, ob(j + 1) = ob(j) + len(j) + gap, total = ob(k)       (k == 0: total = lead)
+ *     d_out[ob(j), ob(j) + len(j)) = T(j); every other byte of d_out[0, total) = fill
+ *     d_out_begin[j] = ob(j), d_out_end[j] = ob(j) + len(j)               (k uint64 each; either may be NULL)
+ * T(j), byte for byte what Python writes:
+ *     INT64, UINT64   str(int): a `-` for negatives only, no `+`, no leading zeros, 1 to 20 bytes
+ *     FLOAT64         repr(float).  The digits are the shortest string of 1 to 17 that reads back as the same double, and
+ *                     among the strings of that length the one closest to the exact value (the even one at a tie).  With the
+ *                     value written 0.d1d2... x 10^decpt the form is positional for -4 < decpt <= 16, `.0` appended when
+ *                     there is no fraction (9999999999999998.0, 0.0001, 1000000000000000.5), else d[.ddd]e+-XX with a sign and
+ *                     at least two exponent digits (1e+16, 1e-05, 1.2345678901234568e+17, 5e-324).  -0.0 is `-0.0`.  The
+ *                     non-finite values are `inf`, `-inf` and `nan`, whatever the NaN's sign and payload: THESE THREE
+ *                     rj_scan_records_parse DOES NOT READ BACK (its grammar has digits only: they are MALFORMED there).
+ *                     The longest row has 24 bytes (-2.9205048131065683e-196).
+ *     d_status given  a row whose d_status[r(j)] (n_values bytes: parse's status column, unchanged) is not RJ_PARSE_OK is the
+ *                     EMPTY row: zero bytes, an empty CSV field, Arrow's null.
+ * For every finite double, rj_scan_records_parse(RJ_PARSE_FLOAT64, RJ_PARSE_WIDE) of the output returns the input's bits with
+ * status OK; the integer kinds likewise return the value.  The digits are computed in integers only (Schubfach over a table of
+ * 128-bit powers of ten, rejit_amd/csrc/pow10_table.h); there is no fallback and no floating-point operation.
+ * flags must be 0: every bit is refused, later styles have room.  fill: 0..255; gap may be 0.  d_out: 16-byte aligned, out_cap
+ * bytes.  Returns total WHATEVER out_cap is and never writes at or beyond out_cap; d_out == NULL with out_cap == 0 is the size
+ * query (the tables are still written when given).  With total <= out_cap the result is complete: every byte of [0, total) and
+ * every table row is written exactly once, nothing has to be cleared first, nothing behind total or behind row k is touched.
+ * The scan lends scratch only: spans, stats and the state of its last rj_scan_records (rj_scan_records_select included) stay as
+ * they were.  One synchronise per call.
+ * Refusals (RJ_BAD_ARGUMENT; a refused call writes no output byte and no table row): an index >= n_values -- the message names
+ * the first bad row, "row <j> " --; a null d_value with n_values > 0, a null d_out with out_cap > 0; a table, d_value or
+ * d_indices that is not 8-byte aligned; a d_out that is not 16-byte aligned; an unknown kind, any flag bit, a fill outside
+ * 0..255; 24 + gap >= 2^42, or lead + k * (24 + gap) >= 2^62.  k >= 2^31: RJ_TOO_LARGE, as in the rest of the family's row
+ * calls.  An output that overlaps an input is undefined, as elsewhere in the family. */
+#define RJ_FORMAT_INT64 0 /* the kind numbers of RJ_PARSE_* */
+#define RJ_FORMAT_UINT64 1
+#define RJ_FORMAT_FLOAT64 2
+int64_t rj_scan_records_format(rj_scan* scan, const uint64_t* d_value, const uint8_t* d_status /* may be NULL */,
+                               uint64_t n_values, const uint64_t* d_indices, uint64_t n_indices, int kind, unsigned flags,
+                               int fill, uint64_t lead, uint64_t gap, void* d_out, uint64_t out_cap,
+                               uint64_t* d_out_begin, uint64_t* d_out_end, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

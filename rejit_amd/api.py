@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "pow5_table.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_format.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -213,7 +213,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_format"]
 
 
 def load_library():
@@ -329,6 +329,8 @@ def load_library():
     L.rj_scan_records_lookup.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, vp, ctypes.POINTER(_LookupStats), vp]
     L.rj_scan_records_parse.restype = i64
     L.rj_scan_records_parse.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_uint, vp, vp, ctypes.POINTER(_ParseStats), vp]
+    L.rj_scan_records_format.restype = i64
+    L.rj_scan_records_format.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_uint, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
     _lib = L
     return L
 
@@ -937,6 +939,57 @@ class Scan:
         if stats:
             return values, status, {f: int(getattr(out, f)) for f, _ in _ParseStats._fields_}
         return values, status
+
+    def format_records(self, values, kind=None, status=None, indices=None, fill: int = 10, lead: int = 0, gap: int = 1, out=None, stream=None, flags: int = 0):
+        """rj_scan_records_format: the inverse of parse_records -- a column of numbers written as decimal text on the device,
+        laid out as pack_records lays records out.  `values` is an int64 or float64 device tensor; kind is "int64", "uint64" or
+        "float64" and defaults from the dtype ("uint64" takes the int64 tensor of bits parse_records returns).  Row j is
+        Python's str(int) / repr(float) of values[indices[j]] (or values[j]), byte for byte -- the shortest digits that read
+        back as the same double, `inf`, `-inf`, `nan` for the non-finite ones --, or the EMPTY row where `status` (uint8,
+        parse_records' status column) is given and not PARSE_OK.  Returns (out_text, out_begin, out_end) as pack_records does:
+        `gap` bytes of `fill` (default: a newline) behind every row, `lead` in front; without `out` one size query and an
+        exact allocation, with `out` (contiguous uint8, 16-byte aligned) one call and RejitError when it is too small.
+        parse_records(out_text, out_begin, out_end, kind=kind, wide=True) gives every finite value's bits back.  `flags` must
+        be 0 (no style is defined yet).  The scan's spans, stats and select_records stay as they were."""
+        import torch
+
+        v = values
+        assert v.is_contiguous() and v.is_cuda and v.dim() == 1
+        if kind is None:
+            kind = {torch.int64: "int64", torch.float64: "float64"}.get(v.dtype)
+        if kind not in PARSE_KINDS:
+            raise ValueError("format_records: kind is 'int64', 'uint64' or 'float64', not %r" % (kind,))
+        assert v.dtype == (torch.float64 if kind == "float64" else torch.int64)
+        n_values = int(v.numel())
+        if status is not None:
+            assert status.dtype == torch.uint8 and status.is_contiguous() and status.device == v.device and status.numel() == n_values
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == v.device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=v.device)   # (a non-null pointer: NULL means every value)
+        else:
+            k = n_values
+        st = torch.cuda.current_stream(v.device).cuda_stream if stream is None else stream
+        out_begin = torch.empty(k, dtype=torch.int64, device=v.device)
+        out_end = torch.empty(k, dtype=torch.int64, device=v.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+
+        def call(buf, cap):
+            return int(_check(self._lib.rj_scan_records_format(self._h, ptr(v), ptr(status), n_values, ptr(indices), k, PARSE_KINDS[kind], int(flags),
+                                                               int(fill), int(lead), int(gap), ptr(buf) if cap else None, cap, ptr(out_begin), ptr(out_end),
+                                                               ctypes.c_void_p(st))))
+        if out is None:
+            total = call(None, 0)
+            out = torch.empty(total, dtype=torch.uint8, device=v.device)
+            if total:
+                call(out, total)
+            return out, out_begin, out_end
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == v.device
+        total = call(out, int(out.numel()))
+        if total > out.numel():
+            raise RejitError(-4, "format_records: the text has %d bytes, `out` %d" % (total, out.numel()))
+        return out[:total], out_begin, out_end
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""

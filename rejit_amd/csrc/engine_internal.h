@@ -173,6 +173,9 @@ struct rj_scan {
   rejit_amd::DeviceBuffer rec_pack_begin;
   // rj_scan_records_replace (record_replace.hip) shares all of that and with_buf; rec_repl_table: its per-match table D
   rejit_amd::DeviceBuffer rec_repl_table;
+  // rj_scan_records_format (record_format.hip) shares the summary, the look-back words and rec_pack_begin; rec_format_stage:
+  // the 16 bytes per row between its plan and its emit
+  rejit_amd::DeviceBuffer rec_format_stage;
   unsigned long long* rec_host = nullptr;
   const uint32_t* rec_select_counts = nullptr;
   uint64_t rec_n = 0;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-D] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -44,6 +44,9 @@ answer on the GPU:
        in a line break, as `grep -f` reads it), and rj_scan_records_lookup looks the lines or the fields up in them on the
        device: only the count (-c), the numbers (-n) or the packed lines (-p) come back.  Beside -k only -c, -n, -p, -v and
        -f N are allowed.
+  -D   numbers as text from the device: with -n the 1-based line numbers, with -a M / -A M the sums, are written as decimal
+       text by rj_scan_records_format -- str(int) / repr(float), byte for byte -- and only that packed text is downloaded,
+       not the values; the output is the output without -D
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -80,8 +83,8 @@ def main(argv):
     if "-A" in argv[:-1] and agg is None:
         at = argv.index("-A")
         agg, agg_float, argv = argv[at + 1], True, argv[:at] + argv[at + 2:]
-    matches_out, unique, byte_order = "-o" in argv, "-u" in argv, "-b" in argv
-    argv = [a for a in argv if a not in ("-o", "-u", "-b")]
+    matches_out, unique, byte_order, device_text = "-o" in argv, "-u" in argv, "-b" in argv, "-D" in argv
+    argv = [a for a in argv if a not in ("-o", "-u", "-b", "-D")]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
     if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)) or (top is not None and (not top.isdigit() or not unique)) or (
@@ -138,7 +141,10 @@ def main(argv):
             lines = torch.nonzero(keep).reshape(-1)
         lines = lines.contiguous()
         selected = int(lines.numel())
-        if numbers:
+        if numbers and device_text:
+            sys.stdout.flush()
+            sys.stdout.buffer.write(scan.format_records(lines + 1)[0].cpu().numpy().tobytes())
+        elif numbers:
             sys.stdout.write("".join("%d\n" % (i + 1) for i in lines.cpu().tolist()))
         elif lines_out:
             if selected:
@@ -185,7 +191,10 @@ def main(argv):
                 packed, _, _ = scan.pack_records(text, pb, pe, indices=rep if keep is None else keep[rep], fill=10, lead=0, gap=1)
                 words = packed.cpu().numpy().tobytes().split(b"\n")     # the dictionary and the counts: the only downloads
                 sys.stdout.flush()
-                if sums is None:
+                if sums is not None and device_text:                    # the sums as one packed text: its lines are the third column
+                    sum_words = scan.format_records(sums.contiguous())[0].cpu().numpy().tobytes().split(b"\n")
+                    sys.stdout.buffer.write(b"".join(b"%7d %s %s\n" % (c, w, a) for c, w, a in zip(count.cpu().tolist(), words, sum_words)))
+                elif sums is None:
                     sys.stdout.buffer.write(b"".join(b"%7d %s\n" % (c, w) for c, w in zip(count.cpu().tolist(), words)))
                 elif agg_float:
                     sys.stdout.buffer.write(b"".join(b"%7d %s %s\n" % (c, w, repr(a).encode()) for c, w, a in zip(count.cpu().tolist(), words, sums.cpu().tolist())))
@@ -199,7 +208,11 @@ def main(argv):
                 sys.stdout.flush()
                 sys.stdout.buffer.write(packed.cpu().numpy().tobytes())   # the only download besides the summary
         return 0 if selected or (every and field is not None) else 1
-    if numbers:
+    if numbers and device_text:
+        lines = scan.select_records(invert=invert)
+        sys.stdout.flush()
+        sys.stdout.buffer.write(scan.format_records(lines + 1)[0].cpu().numpy().tobytes())   # the only download besides the summary
+    elif numbers:
         lines = scan.select_records(invert=invert)                   # the only download besides the summary
         sys.stdout.write("".join("%d\n" % (i + 1) for i in lines.cpu().tolist()))
     elif lines_out:
