@@ -524,6 +524,49 @@ int64_t rj_scan_records_format(rj_scan* scan, const uint64_t* d_value, const uin
                                uint64_t n_values, const uint64_t* d_indices, uint64_t n_indices, int kind, unsigned flags,
                                int fill, uint64_t lead, uint64_t gap, void* d_out, uint64_t out_cap,
                                uint64_t* d_out_begin, uint64_t* d_out_end, void* hip_stream);
+/* Several columns of records put SIDE BY SIDE into lines (rejit_amd/csrc/record_zip.hip): the inverse
+ * of rj_scan_records_split -- Arrow's binary_join_element_wise, `paste -d`, `awk '{print $3, $1}'`, the "%7d %s %s\n" of
+ * `sort | uniq -c` -- as a new device text and its record table, without a download.  cols: n_cols (1..16) columns, a HOST
+ * array.  Column c is a record table over a device text of its own -- d_text (n bytes), d_rec_begin, d_rec_end (n_records) --,
+ * an optional index list and a width; its rows are rj_scan_records_pack's: row j is record d_indices ? d_indices[j] : j, any
+ * order, repeats allowed, a non-NULL list with count 0 is no rows; every row keeps begin <= end <= n, every index is
+ * < n_records.  Columns may share one text and one table (two fields of one split).  Every column has the same row count
+ * k = d_indices ? n_indices : n_records.  With P(c, j) the bytes of column c's row j:
+ *     F(c, j) = P(c, j) padded to |width| bytes with the byte `pad`: a positive width pads on the LEFT (%7d), a negative one
+ *               on the RIGHT (%-7s); width 0, or a piece already that long, adds nothing; nothing is ever truncated
+ *     T(j)    = F(0, j) sep F(1, j) sep ... F(C-1, j)        sep: sep_len (0..64) HOST bytes, the same between every pair
+ * and the layout is rj_scan_records_pack's with len(j) = |T(j)|:
+ *     ob(0) = lead, ob(j + 1) = ob(j) + len(j) + gap, total = ob(k)       (k == 0: total = lead)
+ *     d_out[ob(j), ob(j) + len(j)) = T(j); every other byte of d_out[0, total) = fill
+ *     d_out_begin[j] = ob(j), d_out_end[j] = ob(j) + len(j)               (k uint64 each; either may be NULL)
+ * With n_cols = 1 and width 0 the output is rj_scan_records_pack's for the same arguments, byte for byte and table row for
+ * table row, whatever sep is.  The columns and the separator travel as kernel arguments: no upload, no allocation for them.
+ * flags must be 0.  pad, fill: 0..255; gap may be 0.  d_out: 16-byte aligned, out_cap bytes.  Returns total WHATEVER out_cap
+ * is and never writes at or beyond out_cap; d_out == NULL with out_cap == 0 is the size query (the tables are still written
+ * when given).  With total <= out_cap the result is complete: every byte of [0, total) and every table row is written exactly
+ * once, nothing has to be cleared first, nothing behind total or behind row k is touched.  The scan lends scratch only (8 +
+ * 16 n_cols bytes per row): spans, stats and the state of its last rj_scan_records stay as they were.  One synchronise per call.
+ * Refusals (RJ_BAD_ARGUMENT; a refused call writes no output byte and no table row): a bad index or a bad row in any column
+ * -- the message names the first one, "row <j> column <c> ": the smallest j, and at that j the smallest c --; n_cols outside
+ * 1..16; columns whose k differ (both are named); sep == NULL with sep_len > 0; sep_len > 64; |width| > 4096; reserved != 0;
+ * any flag bit; pad or fill outside 0..255; a null text with n > 0, a null table with k > 0, a null d_out with out_cap > 0; a
+ * table or index list that is not 8-byte aligned; a d_out that is not 16-byte aligned; R >= 2^42 with R = sum over the columns
+ * of max(n, |width|) + (n_cols - 1) sep_len + gap, or lead + k R >= 2^62.  k >= 2^31: RJ_TOO_LARGE.  An output that overlaps
+ * an input is undefined, as elsewhere in the family. */
+typedef struct rj_zip_column {
+  const void* d_text;
+  uint64_t n;
+  const uint64_t* d_rec_begin;
+  const uint64_t* d_rec_end;
+  uint64_t n_records;
+  const uint64_t* d_indices; /* may be NULL */
+  uint64_t n_indices;
+  int32_t width;
+  int32_t reserved; /* must be 0 */
+} rj_zip_column;    /* 64 bytes */
+int64_t rj_scan_records_zip(rj_scan* scan, const rj_zip_column* cols, int n_cols, const char* sep, uint64_t sep_len, int pad,
+                            unsigned flags, int fill, uint64_t lead, uint64_t gap, void* d_out, uint64_t out_cap,
+                            uint64_t* d_out_begin, uint64_t* d_out_end, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

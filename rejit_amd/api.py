@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_format.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_format.hip", "record_zip.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -174,6 +174,13 @@ class _ParseStats(ctypes.Structure):
                 ("n_inexact", ctypes.c_uint64)]
 
 
+class ZipColumn(ctypes.Structure):
+    """rj_zip_column: one column of rj_scan_records_zip (64 bytes)"""
+    _fields_ = [("d_text", ctypes.c_void_p), ("n", ctypes.c_uint64), ("d_rec_begin", ctypes.c_void_p), ("d_rec_end", ctypes.c_void_p),
+                ("n_records", ctypes.c_uint64), ("d_indices", ctypes.c_void_p), ("n_indices", ctypes.c_uint64), ("width", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 PARSE_KINDS = {"int64": 0, "uint64": 1, "float64": 2}                      # RJ_PARSE_INT64, _UINT64, _FLOAT64
 PARSE_TRIM, PARSE_WIDE = 1, 4                                              # flags (RJ_PARSE_TRIM, RJ_PARSE_WIDE; 2 is reserved)
 PARSE_OK, PARSE_EMPTY, PARSE_MALFORMED, PARSE_RANGE, PARSE_INEXACT = range(5)   # a row's status (RJ_PARSE_OK, ...)
@@ -213,7 +220,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_format"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_format", "rj_scan_records_zip"]
 
 
 def load_library():
@@ -331,6 +338,8 @@ def load_library():
     L.rj_scan_records_parse.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_uint, vp, vp, ctypes.POINTER(_ParseStats), vp]
     L.rj_scan_records_format.restype = i64
     L.rj_scan_records_format.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_uint, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
+    L.rj_scan_records_zip.restype = i64
+    L.rj_scan_records_zip.argtypes = [vp, ctypes.POINTER(ZipColumn), ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int, ctypes.c_uint, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
     _lib = L
     return L
 
@@ -989,6 +998,70 @@ class Scan:
         total = call(out, int(out.numel()))
         if total > out.numel():
             raise RejitError(-4, "format_records: the text has %d bytes, `out` %d" % (total, out.numel()))
+        return out[:total], out_begin, out_end
+
+    def zip_records(self, columns, sep: bytes = b"", widths=None, pad: int = 32, fill: int = 10, lead: int = 0, gap: int = 1, out=None, stream=None,
+                    flags: int = 0):
+        """rj_scan_records_zip: the inverse of split_records -- the rows of several columns put side by side into lines on the
+        device.  `columns` is a list (1 to 16) of (text, rec_begin, rec_end) or (text, rec_begin, rec_end, indices): each a
+        record table over a uint8 device text of its own (several may share one), rows as pack_records takes them; every
+        column has the same number of rows.  Line j is the columns' rows j joined with `sep` (bytes, at most 64), column c
+        padded with the byte `pad` to |widths[c]| bytes first: on the left for a positive width ("%7d"), on the right for a
+        negative one ("%-7s"); 0, the default, adds nothing, and nothing is truncated.  Returns (out_text, out_begin, out_end)
+        as pack_records does: `gap` bytes of `fill` (default: a newline) behind every line, `lead` in front; without `out` one
+        size query and an exact allocation, with `out` (contiguous uint8, 16-byte aligned) one call and RejitError when it is
+        too small.  The scan's spans, stats and select_records stay as they were."""
+        import torch
+
+        columns = [tuple(c) for c in columns]
+        widths = [0] * len(columns) if widths is None else [int(w) for w in widths]
+        if len(widths) != len(columns):
+            raise ValueError("zip_records: %d widths for %d columns" % (len(widths), len(columns)))
+        if not columns:
+            raise RejitError(-4, "zip_records: no columns (a call takes 1 to 16)")
+        sep = bytes(sep)
+        device = columns[0][0].device
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else 0
+        cols = (ZipColumn * len(columns))()
+        keep = []
+        k = None
+        for c, column in enumerate(columns):
+            if len(column) not in (3, 4):
+                raise ValueError("zip_records: a column is (text, rec_begin, rec_end) or (text, rec_begin, rec_end, indices)")
+            t, rb, re_ = column[:3]
+            indices = column[3] if len(column) == 4 else None
+            assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda and t.device == device
+            n_records = int(rb.numel())
+            for x in (rb, re_):
+                assert x.dtype == torch.int64 and x.is_contiguous() and x.device == device and x.numel() == n_records
+            rows = n_records
+            if indices is not None:
+                assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == device
+                rows = int(indices.numel())
+                if rows == 0:
+                    indices = torch.zeros(1, dtype=torch.int64, device=device)   # (a non-null pointer: NULL means every record)
+                    keep.append(indices)
+            k = rows if k is None else k
+            cols[c] = ZipColumn(ptr(t), int(t.numel()), ptr(rb), ptr(re_), n_records, indices.data_ptr() if indices is not None else 0,
+                                rows if indices is not None else 0, widths[c], 0)
+        st = torch.cuda.current_stream(device).cuda_stream if stream is None else stream
+        out_begin = torch.empty(k, dtype=torch.int64, device=device)
+        out_end = torch.empty(k, dtype=torch.int64, device=device)
+
+        def call(buf, cap):
+            return int(_check(self._lib.rj_scan_records_zip(self._h, cols, len(columns), sep, len(sep), int(pad), int(flags), int(fill), int(lead), int(gap),
+                                                            ctypes.c_void_p(ptr(buf)) if cap else None, cap, ctypes.c_void_p(ptr(out_begin)),
+                                                            ctypes.c_void_p(ptr(out_end)), ctypes.c_void_p(st))))
+        if out is None:
+            total = call(None, 0)
+            out = torch.empty(total, dtype=torch.uint8, device=device)
+            if total:
+                call(out, total)
+            return out, out_begin, out_end
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == device
+        total = call(out, int(out.numel()))
+        if total > out.numel():
+            raise RejitError(-4, "zip_records: the text has %d bytes, `out` %d" % (total, out.numel()))
         return out[:total], out_begin, out_end
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:

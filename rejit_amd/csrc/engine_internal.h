@@ -176,6 +176,9 @@ struct rj_scan {
   // rj_scan_records_format (record_format.hip) shares the summary, the look-back words and rec_pack_begin; rec_format_stage:
   // the 16 bytes per row between its plan and its emit
   rejit_amd::DeviceBuffer rec_format_stage;
+  // rj_scan_records_zip (record_zip.hip) shares the summary, the look-back words and rec_pack_begin; rec_zip_stage: the rows'
+  // lengths (8 bytes per row), then the 16 bytes per piece between its resolve and its emit
+  rejit_amd::DeviceBuffer rec_zip_stage;
   unsigned long long* rec_host = nullptr;
   const uint32_t* rec_select_counts = nullptr;
   uint64_t rec_n = 0;

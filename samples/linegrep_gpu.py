@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-D] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-D] [-Z] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -47,6 +47,10 @@ answer on the GPU:
   -D   numbers as text from the device: with -n the 1-based line numbers, with -a M / -A M the sums, are written as decimal
        text by rj_scan_records_format -- str(int) / repr(float), byte for byte -- and only that packed text is downloaded,
        not the values; the output is the output without -D
+  -Z   (implies -D) with -u: the printed lines themselves are made on the device -- rj_scan_records_zip puts the counts
+       (rj_scan_records_format's text, width 7), the distinct values (their rows straight from the file's text) and, with
+       -a M / -A M, the formatted sums side by side with a space between -- and that one text is the only download; the output
+       is the output without -Z
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -83,8 +87,9 @@ def main(argv):
     if "-A" in argv[:-1] and agg is None:
         at = argv.index("-A")
         agg, agg_float, argv = argv[at + 1], True, argv[:at] + argv[at + 2:]
-    matches_out, unique, byte_order, device_text = "-o" in argv, "-u" in argv, "-b" in argv, "-D" in argv
-    argv = [a for a in argv if a not in ("-o", "-u", "-b", "-D")]
+    matches_out, unique, byte_order, device_zip = "-o" in argv, "-u" in argv, "-b" in argv, "-Z" in argv
+    device_text = "-D" in argv or device_zip
+    argv = [a for a in argv if a not in ("-o", "-u", "-b", "-D", "-Z")]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
     if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)) or (top is not None and (not top.isdigit() or not unique)) or (
@@ -188,6 +193,14 @@ def main(argv):
                 if top is not None:
                     count, rep, order = records.top_groups(count, rep, int(top))
                     sums = None if sums is None else sums[order]
+                if device_zip:                                          # the lines as one text: the only download
+                    columns = [scan.format_records(count.to(torch.int64).contiguous()), (text, pb, pe, (rep if keep is None else keep[rep]).contiguous())]
+                    if sums is not None:
+                        columns.append(scan.format_records(sums.contiguous()))
+                    zipped, _, _ = scan.zip_records(columns, sep=b" ", widths=[7] + [0] * (len(columns) - 1))
+                    sys.stdout.flush()
+                    sys.stdout.buffer.write(zipped.cpu().numpy().tobytes())
+                    return 0 if selected or (every and field is not None) else 1
                 packed, _, _ = scan.pack_records(text, pb, pe, indices=rep if keep is None else keep[rep], fill=10, lead=0, gap=1)
                 words = packed.cpu().numpy().tobytes().split(b"\n")     # the dictionary and the counts: the only downloads
                 sys.stdout.flush()
