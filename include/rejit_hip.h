@@ -482,6 +482,60 @@ int64_t rj_scan_records_parse(rj_scan* scan, const void* d_text, uint64_t n, con
                               const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
                               int kind, unsigned flags, uint64_t* d_value, uint8_t* d_status /* may be NULL */,
                               rj_parse_stats* stats /* may be NULL */, void* hip_stream);
+/* The rows of a record table read AS TIMESTAMPS (rejit_amd/csrc/record_time.hip): the first column of a
+ * log -- `10/Oct/2000:13:55:36 -0700`, `2026-10-20T17:15:00.123Z` --, Arrow's strptime / cast(utf8 -> timestamp[unit]): "requests
+ * per minute", "the lines between two instants", "order by time" -- exactly, or not at all, without a download.  The parse's
+ * fourth value kind: everything that is not about time is rj_scan_records_parse's, word for word -- the row rules, k, the
+ * status enum, rj_parse_stats, the refusals of rows and arguments.
+ *     d_value[j]  = the row's instant as an int64 count of `unit`s since 1970-01-01T00:00:00Z (negative before it); 0 when the
+ *                   status is not OK                                                                              (k uint64)
+ *     d_status[j] = RJ_PARSE_OK, or why the row has no value                                          (k bytes, may be NULL)
+ * `format` (format_len bytes, 1..64; it need not end in a NUL, and a NUL inside is a literal) is a strptime-style format.  A
+ * row is matched against it from its first byte to its last; D is [0-9]:
+ *     %Y   exactly DDDD, 0001..9999 (0000 is RANGE)          %H %M %S   exactly DD each: 00..23, 00..59, 00..59 (a second of
+ *     %m   exactly DD, 01..12                                           60 is RANGE: there are no leap seconds)
+ *     %b   exactly 3 ASCII letters, jan..dec in any case;    %f   1 to 9 digits, as many as the row has there (greedy): the
+ *          other letters or bytes are MALFORMED                   fraction of a second
+ *     %d   exactly DD, 01..the last day of that month in     %z   `Z` (upper case only), or [+-]DD, an optional `:`, DD: hours
+ *          that year (proleptic Gregorian leap rule)              00..23, minutes 00..59 (else RANGE).  The offset is subtracted;
+ *     %%   a `%`                                                  -00:00 is +00:00.  An offset with seconds is MALFORMED
+ *     any other byte, NUL included: itself, exactly.  A blank in the format is one such byte, not "any white space".
+ * Fields the format does not name are 0; without %z the fields are UTC.  With RJ_PARSE_TRIM the ASCII spaces and tabs before
+ * and behind the row are dropped first; without it they are ordinary bytes.  The statuses, decided in this order:
+ *     RJ_PARSE_EMPTY      no bytes are left
+ *     RJ_PARSE_MALFORMED  the row ends before the format does, a byte does not fit its directive or literal, or bytes remain
+ *                         behind the format's last one
+ *     RJ_PARSE_RANGE      a field is outside its range above (the day is judged against its month and year wherever they
+ *                         stand in the row); or the instant is outside int64 in `unit` -- only RJ_TIME_NANO can do that: before
+ *                         1677-09-21T00:12:43.145224192Z or after 2262-04-11T23:47:16.854775807Z
+ *     RJ_PARSE_INEXACT    %f has a non-zero digit below `unit`: the instant is not representable.  Never truncated or rounded
+ * An OK value is what Python's datetime.strptime makes of the same bytes and format -- the civil fields as UTC, or the aware
+ * value under %z -- as (dt - epoch) // unit, computed in integers (days from the civil date by the 400-year-era formula, no
+ * table of years).  Python accepts more (one-digit fields, runs of white space, other letter cases of literals, offsets with
+ * seconds): those rows are MALFORMED here.  No row that is OK here has another value there, and no row Python rejects is OK
+ * here, except for %f with 7 to 9 digits, which Python does not read.
+ * Returns n_ok.  Every row of d_value, and of d_status when given, is written exactly once, nothing has to be cleared first,
+ * nothing behind k is touched; k == 0 returns 0.  `stats` (may be NULL) receives the five counts; they add up to k.  A row of
+ * any length is legal (one lane walks it; a malformed row stops at its first bad byte).  The scan lends scratch only: spans,
+ * stats and the state of its last rj_scan_records (rj_scan_records_select included) stay as they were.  One synchronise per call.
+ * Refusals (RJ_BAD_ARGUMENT; a refused call writes no output row and is never led outside the text or a table): the parse's --
+ * an index >= n_records; a row without begin <= end <= n, the message names the first bad row, "row <j> "; a null argument
+ * (also `format` with format_len > 0); a table or d_value that is not 8-byte aligned --; a unit that is not RJ_TIME_*; a flag
+ * bit other than RJ_PARSE_TRIM; and a format that is refused, the message naming the byte offset, "format byte <i>: ": an
+ * empty format (0); more than 64 bytes (64); an unknown directive or a `%` as the last byte (the `%`); a directive given twice,
+ * or %m together with %b (the second one's `%`); %f directly followed by a digit literal or by one of %Y %m %d %H %M %S (that
+ * byte: the greedy read would be ambiguous); a format without %Y, %d and one of %m / %b (format_len: time-of-day-only formats
+ * stay out).  k >= 2^31: RJ_TOO_LARGE.
+ * What stays out: the inverse (timestamps as text), %y %j %e %a %p, named zones, locales, leap seconds. */
+#define RJ_TIME_SECOND 0
+#define RJ_TIME_MILLI 1
+#define RJ_TIME_MICRO 2
+#define RJ_TIME_NANO 3
+int64_t rj_scan_records_parse_time(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                                   const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices,
+                                   uint64_t n_indices, const char* format, uint64_t format_len, int unit, unsigned flags,
+                                   uint64_t* d_value, uint8_t* d_status /* may be NULL */,
+                                   rj_parse_stats* stats /* may be NULL */, void* hip_stream);
 /* A column of numbers written AS DECIMAL TEXT (rejit_amd/csrc/record_format.hip): the inverse of
  * rj_scan_records_parse -- the sums of an aggregation, line numbers, Arrow's cast(int64 / uint64 / float64 -> utf8) -- as a new
  * device text and its record table, without a download.  d_value: n_values 64-bit words, read by `kind` (the kind numbers of

@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_format.hip", "record_zip.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -183,6 +183,7 @@ class ZipColumn(ctypes.Structure):
 
 PARSE_KINDS = {"int64": 0, "uint64": 1, "float64": 2}                      # RJ_PARSE_INT64, _UINT64, _FLOAT64
 PARSE_TRIM, PARSE_WIDE = 1, 4                                              # flags (RJ_PARSE_TRIM, RJ_PARSE_WIDE; 2 is reserved)
+TIME_UNITS = {"s": 0, "ms": 1, "us": 2, "ns": 3}                             # RJ_TIME_SECOND, _MILLI, _MICRO, _NANO
 PARSE_OK, PARSE_EMPTY, PARSE_MALFORMED, PARSE_RANGE, PARSE_INEXACT = range(5)   # a row's status (RJ_PARSE_OK, ...)
 
 
@@ -220,7 +221,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_format", "rj_scan_records_zip"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip"]
 
 
 def load_library():
@@ -336,6 +337,8 @@ def load_library():
     L.rj_scan_records_lookup.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, vp, ctypes.POINTER(_LookupStats), vp]
     L.rj_scan_records_parse.restype = i64
     L.rj_scan_records_parse.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_uint, vp, vp, ctypes.POINTER(_ParseStats), vp]
+    L.rj_scan_records_parse_time.restype = i64
+    L.rj_scan_records_parse_time.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, cp, u64, ctypes.c_int, ctypes.c_uint, vp, vp, ctypes.POINTER(_ParseStats), vp]
     L.rj_scan_records_format.restype = i64
     L.rj_scan_records_format.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_uint, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
     L.rj_scan_records_zip.restype = i64
@@ -945,6 +948,49 @@ class Scan:
         out = _ParseStats()
         _check(self._lib.rj_scan_records_parse(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k, PARSE_KINDS[kind],
                                                (PARSE_TRIM if trim else 0) | (PARSE_WIDE if wide else 0), ptr(values), ptr(status), ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
+        if stats:
+            return values, status, {f: int(getattr(out, f)) for f, _ in _ParseStats._fields_}
+        return values, status
+
+    def parse_time_records(self, text_tensor, rec_begin, rec_end, fmt, indices=None, unit="s", trim=False, stats=False, stream=None):
+        """rj_scan_records_parse_time: the rows text[rec_begin[i], rec_end[i]) -- all of them, or those `indices` names, as
+        parse_records' -- read as timestamps under the strptime-style format `fmt` (bytes or str, 1..64 bytes): Arrow's
+        strptime / cast(utf8 -> timestamp[unit]).  The directives are %Y %m %b %d %H %M %S %f %z %%, every field of exactly
+        its digits (%f: 1 to 9, greedy; %b: jan..dec in any case; %z: Z or [+-]hh[:]mm), every other byte of the format a
+        literal; without %z the fields are UTC.  unit is "s", "ms", "us" or "ns"; trim=True drops the spaces and tabs before
+        and behind the row first.  Returns (values, status), device tensors of k entries: values (int64) holds the count of
+        units since 1970-01-01T00:00:00Z of an OK row -- what datetime.strptime makes of it, as (dt - epoch) // unit -- and 0
+        for every other row; status (uint8) is PARSE_OK, PARSE_EMPTY, PARSE_MALFORMED, PARSE_RANGE (a field outside its range,
+        the day against its month and year; under "ns" an instant outside int64) or PARSE_INEXACT (a non-zero fraction digit
+        below the unit: never truncated or rounded).  With stats=True also {"n_ok", "n_empty", "n_malformed", "n_range",
+        "n_inexact"}.  records.time_buckets floors the values to buckets.  RejitError (RJ_BAD_ARGUMENT) for a bad index or row
+        (naming the first bad row) and for a refused format (naming the byte offset).  The scan's spans, stats and
+        select_records stay as they were.  The inverse, %y %j %e %a %p, named zones, locales and leap seconds stay out."""
+        import torch
+
+        t = text_tensor
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        if unit not in TIME_UNITS:
+            raise ValueError("parse_time_records: unit is 's', 'ms', 'us' or 'ns', not %r" % (unit,))
+        fmt = fmt.encode("utf-8") if isinstance(fmt, str) else bytes(fmt)
+        n_records = int(rec_begin.numel())
+        for x in (rec_begin, rec_end):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
+        else:
+            k = n_records
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        values = torch.empty(k, dtype=torch.int64, device=t.device)
+        status = torch.empty(k, dtype=torch.uint8, device=t.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        out = _ParseStats()
+        _check(self._lib.rj_scan_records_parse_time(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k, fmt, len(fmt),
+                                                    TIME_UNITS[unit], PARSE_TRIM if trim else 0, ptr(values), ptr(status),
+                                                    ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
         if stats:
             return values, status, {f: int(getattr(out, f)) for f, _ in _ParseStats._fields_}
         return values, status

@@ -166,3 +166,18 @@ def group_counts_ok(group, ok, n_groups: int):
 
     counts = torch.zeros(int(n_groups), dtype=torch.int64, device=group.device)
     return counts.index_add_(0, group, ok.to(torch.int64))
+
+
+def time_buckets(values, status, width: int):
+    """(bucket_start, ok) of Scan.parse_time_records' (values, status): bucket_start[j] = floor(values[j] / width) x width, the
+    floor toward minus infinity, so an instant before 1970 lies in the bucket that begins at or before it (-1 with width 60 is
+    in the bucket -60); ok = status == PARSE_OK, a bool tensor -- the rows that are not ok have the value 0 and must be left
+    out by it.  `width` is a positive count of the values' unit: "requests per minute" is time_buckets(..., 60) over seconds,
+    then torch.unique(bucket_start[ok], return_counts=True).  Torch only and device-agnostic."""
+    import torch
+
+    width = int(width)
+    if width < 1:
+        raise ValueError("time_buckets: width is a positive number of units, not %r" % (width,))
+    start = torch.div(values, width, rounding_mode="floor") * width
+    return start, status == 0

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-D] [-Z] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-D] [-Z] [-T FORMAT -w UNITS] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -51,6 +51,15 @@ answer on the GPU:
        (rj_scan_records_format's text, width 7), the distinct values (their rows straight from the file's text) and, with
        -a M / -A M, the formatted sums side by side with a space between -- and that one text is the only download; the output
        is the output without -Z
+  -T FORMAT -w UNITS   with -f N: field N of every line -- with -p / -v: of every selected line -- is read as a TIMESTAMP under
+       the strptime-style FORMAT (rj_scan_records_parse_time, in seconds, spaces and tabs around the field dropped; the
+       directives are %Y %m %b %d %H %M %S %f %z %%, every other byte a literal; without %z the fields are UTC), and the lines
+       are counted per bucket of UNITS seconds: "%7d %d" -- the count and the bucket's first second since 1970-01-01T00:00:00Z,
+       the floor toward minus infinity -- in ascending bucket order (`awk '{c[int(t($N)/w)*w]++}'` with a t() awk does not
+       have): records.time_buckets and a torch.unique over the int64 values; only the buckets and the counts come back.  A
+       line whose field N is missing, not in FORMAT, out of range (month 13, 30 February, a second of 60) or, under %f, has a
+       non-zero fraction of a second is counted nowhere.  Only -p and -v go with it; a FORMAT the library refuses (an unknown directive, no %Y / %d /
+       month, more than 64 bytes) is an error.  Exit status 0 when a line was counted, else 1
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -87,6 +96,13 @@ def main(argv):
     if "-A" in argv[:-1] and agg is None:
         at = argv.index("-A")
         agg, agg_float, argv = argv[at + 1], True, argv[:at] + argv[at + 2:]
+    time_format = width = None
+    if "-T" in argv[:-1]:
+        at = argv.index("-T")
+        time_format, argv = os.fsencode(argv[at + 1]), argv[:at] + argv[at + 2:]
+    if "-w" in argv[:-1]:
+        at = argv.index("-w")
+        width, argv = argv[at + 1], argv[:at] + argv[at + 2:]
     matches_out, unique, byte_order, device_zip = "-o" in argv, "-u" in argv, "-b" in argv, "-Z" in argv
     device_text = "-D" in argv or device_zip
     argv = [a for a in argv if a not in ("-o", "-u", "-b", "-D", "-Z")]
@@ -95,7 +111,10 @@ def main(argv):
     if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)) or (top is not None and (not top.isdigit() or not unique)) or (
             unique and not matches_out and field is None) or (byte_order and not matches_out and field is None and "-p" not in flags) or (
             keys is not None and (repl is not None or top is not None or matches_out or unique or byte_order or agg is not None)) or (
-            agg is not None and (not agg.isdigit() or int(agg) < 1 or not unique or field is None or matches_out)):
+            agg is not None and (not agg.isdigit() or int(agg) < 1 or not unique or field is None or matches_out)) or (
+            (time_format is None) != (width is None)) or (time_format is not None and (
+                not width.isdigit() or int(width) < 1 or field is None or matches_out or unique or byte_order or device_text or repl is not None
+                or keys is not None or agg is not None or top is not None or "-n" in flags or "-c" in flags)):
         sys.stderr.write(__doc__)
         return 2
     path, pattern = rest
@@ -123,6 +142,23 @@ def main(argv):
     scan = rejit_amd.Scan(rejit_amd.Program(pattern))
     result = scan.run_records(text, begins, ends)
     selected = result.n_records - result.n_matching if invert else result.n_matching
+    if time_format is not None:
+        every = not invert and "-p" not in flags
+        lines = None if every else scan.select_records(invert=invert)
+        counted = 0
+        if every or selected:
+            pb, pe, pf = scan.split_records(begins, ends, result, int(text.numel()), indices=lines, what="between")
+            tb, te, _ = records.field_records(pb, pe, pf, int(field) - 1)     # (a missing field is an empty record: RJ_PARSE_EMPTY)
+            try:
+                values, status = scan.parse_time_records(text, tb, te, time_format, unit="s", trim=True)
+            except rejit_amd.RejitError as err:
+                sys.stderr.write("linegrep_gpu: -T: %s\n" % err.message)
+                return 2
+            start, ok = records.time_buckets(values, status, int(width))
+            buckets, counts = torch.unique(start[ok], return_counts=True)     # ascending; the only downloads
+            counted = int(buckets.numel())
+            sys.stdout.write("".join("%7d %d\n" % (c, b) for b, c in zip(buckets.cpu().tolist(), counts.cpu().tolist())))
+        return 0 if counted else 1
     if keys is not None:
         key_data = np.fromfile(keys, dtype=np.uint8)
         key_text = torch.from_numpy(key_data if key_data.size else np.zeros(1, dtype=np.uint8)).to("cuda:0")     # the second upload
