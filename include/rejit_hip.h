@@ -526,7 +526,8 @@ int64_t rj_scan_records_parse(rj_scan* scan, const void* d_text, uint64_t n, con
  * or %m together with %b (the second one's `%`); %f directly followed by a digit literal or by one of %Y %m %d %H %M %S (that
  * byte: the greedy read would be ambiguous); a format without %Y, %d and one of %m / %b (format_len: time-of-day-only formats
  * stay out).  k >= 2^31: RJ_TOO_LARGE.
- * What stays out: the inverse (timestamps as text), %y %j %e %a %p, named zones, locales, leap seconds. */
+ * The inverse (timestamps as text) is rj_scan_records_format_time, below.  What stays out: %y %j %e %a %p, named zones,
+ * locales, leap seconds. */
 #define RJ_TIME_SECOND 0
 #define RJ_TIME_MILLI 1
 #define RJ_TIME_MICRO 2
@@ -621,6 +622,61 @@ typedef struct rj_zip_column {
 int64_t rj_scan_records_zip(rj_scan* scan, const rj_zip_column* cols, int n_cols, const char* sep, uint64_t sep_len, int pad,
                             unsigned flags, int fill, uint64_t lead, uint64_t gap, void* d_out, uint64_t out_cap,
                             uint64_t* d_out_begin, uint64_t* d_out_end, void* hip_stream);
+/* A column of int64 INSTANTS written AS TEXT (rejit_amd/csrc/record_time_format.hip): the inverse of
+ * rj_scan_records_parse_time -- the buckets of "requests per minute" as `2026-10-20T17:15`, a time column that was filtered or
+ * sorted on the device, Arrow's strftime / cast(timestamp[unit] -> utf8) -- as a new device text and its record table, without
+ * a download.  Everything that is not about time is rj_scan_records_format's, word for word: d_value (n_values 64-bit words),
+ * k = d_indices ? n_indices : n_values, r(j) = d_indices ? d_indices[j] : j (repeats allowed; a non-NULL list with count 0 is
+ * no rows), row j's bytes T(j) made from d_value[r(j)], and the layout with len(j) = |T(j)|:
+ *     ob(0) = lead, ob(j + 1) = ob(j) + len(j) + gap, total = ob(k)       (k == 0: total = lead)
+ *     d_out[ob(j), ob(j) + len(j)) = T(j); every other byte of d_out[0, total) = fill
+ *     d_out_begin[j] = ob(j), d_out_end[j] = ob(j) + len(j)               (k uint64 each; either may be NULL)
+ * The value is an int64 count of `unit`s (RJ_TIME_SECOND .. RJ_TIME_NANO) since 1970-01-01T00:00:00Z.  Its civil instant is
+ * floor(value / units per second) seconds plus a non-negative rest -- the floor goes toward minus infinity: -1 ns is
+ * 1969-12-31T23:59:59.999999999 --, shifted by zone_minutes (-1439..1439, one fixed offset for the whole column; 0 is UTC) and
+ * split by the inverse of the parse's days-from-civil: the 400-year-era formula in integers, no table of years.  `format`
+ * (format_len bytes, 1..64; it need not end in a NUL, and a NUL inside is a literal) has the parse's own directives, every one
+ * of a fixed width:
+ *     %Y   4 digits, zero-padded                             %f   the unit's fraction digits: 3 under MILLI, 6 under MICRO, 9
+ *     %m %d %H %M %S   2 digits each                              under NANO, six zeros under SECOND (Python's %f)
+ *     %b   Jan..Dec                                          %z   +hhmm / -hhmm of zone_minutes, +0000 for 0 (Python's form; the
+ *     %%   a `%`                                                  parse reads it back, its colon is optional)
+ *     any other byte, NUL included: itself
+ * Fields the format does not name are dropped, as strftime drops them: a floor to the finest named field.  Every OK row of a
+ * call therefore has the SAME length L, which depends on the format and the unit only; the longest possible L is 77 (64 format
+ * bytes, + 2 for %Y, + 1 for %b, + 7 for %f, + 3 for %z).  A row is the EMPTY row (zero bytes) in two cases:
+ *     d_status given  d_status[r(j)] (n_values bytes: parse's status column, unchanged) is not RJ_PARSE_OK      (n_null)
+ *     out of range    the SHIFTED instant's year is outside 0001..9999 -- never a nearby or wrapped value       (n_range)
+ *                     Only SECOND, MILLI and MICRO can produce it: every int64 under NANO lies inside 1677..2262.
+ * An OK row is, byte for byte, what Python's datetime.strftime writes for the same instant and format, with two differences:
+ * %Y is isoformat()'s four digits (on glibc datetime(1, 1, 1).strftime('%Y') is '1'), and %f has the unit's digits, where
+ * Python's datetime knows microseconds only.  For every format that names %Y, a month, %d, %H, %M, %S, and %f where the unit
+ * is finer than a second (and %z unless zone_minutes is 0), rj_scan_records_parse_time of the output returns the value with
+ * status OK.  `stats` (may be NULL) receives n_ok, n_null and n_range; they add up to k.
+ * flags must be 0: every bit is refused.  fill: 0..255; gap may be 0.  d_out: 16-byte aligned, out_cap bytes.  Returns total
+ * WHATEVER out_cap is and never writes at or beyond out_cap; d_out == NULL with out_cap == 0 is the size query (the tables are
+ * still written when given).  With total <= out_cap the result is complete: every byte of [0, total) and every table row is
+ * written exactly once, nothing has to be cleared first, nothing behind total or behind row k is touched.  The scan lends
+ * scratch only (16 bytes per row): spans, stats and the state of its last rj_scan_records (rj_scan_records_select included)
+ * stay as they were.  One synchronise per call.
+ * Refusals (RJ_BAD_ARGUMENT; a refused call writes no output byte, no table row and no stats): rj_scan_records_format's -- an
+ * index >= n_values, the message names the first bad row, "row <j> "; a null d_value with n_values > 0, a null d_out with
+ * out_cap > 0; a table, d_value or d_indices that is not 8-byte aligned; a d_out that is not 16-byte aligned; any flag bit; a
+ * fill outside 0..255 --; a null `format` with format_len > 0; a unit that is not RJ_TIME_*; zone_minutes outside -1439..1439;
+ * a format that is refused, the message naming the byte offset, "format byte <i>: ": an empty format (0); more than 64 bytes
+ * (64); an unknown directive or a `%` as the last byte (the `%`); a directive given twice, or %m together with %b (the second
+ * one's `%`) -- the parse's two other refusals do not apply to writing: %f may stand before a digit, and `%H:%M` is a fine
+ * format --; 77 + gap >= 2^42, or lead + k * (77 + gap) >= 2^62.  k >= 2^31: RJ_TOO_LARGE.  An output that overlaps an input
+ * is undefined, as elsewhere in the family.
+ * What stays out: %y %j %e %a %p, named zones and daylight saving, per-row offsets, locales, leap seconds. */
+typedef struct rj_format_time_stats {
+  uint64_t n_ok, n_null, n_range; /* they add up to k */
+} rj_format_time_stats;
+int64_t rj_scan_records_format_time(rj_scan* scan, const uint64_t* d_value, const uint8_t* d_status /* may be NULL */,
+                                    uint64_t n_values, const uint64_t* d_indices, uint64_t n_indices, const char* format,
+                                    uint64_t format_len, int unit, int zone_minutes, unsigned flags, int fill, uint64_t lead,
+                                    uint64_t gap, void* d_out, uint64_t out_cap, uint64_t* d_out_begin, uint64_t* d_out_end,
+                                    rj_format_time_stats* stats /* may be NULL */, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "record_time_format.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_time_format.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -174,6 +174,10 @@ class _ParseStats(ctypes.Structure):
                 ("n_inexact", ctypes.c_uint64)]
 
 
+class _FormatTimeStats(ctypes.Structure):
+    _fields_ = [("n_ok", ctypes.c_uint64), ("n_null", ctypes.c_uint64), ("n_range", ctypes.c_uint64)]
+
+
 class ZipColumn(ctypes.Structure):
     """rj_zip_column: one column of rj_scan_records_zip (64 bytes)"""
     _fields_ = [("d_text", ctypes.c_void_p), ("n", ctypes.c_uint64), ("d_rec_begin", ctypes.c_void_p), ("d_rec_end", ctypes.c_void_p),
@@ -221,7 +225,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip", "rj_scan_records_format_time"]
 
 
 def load_library():
@@ -343,6 +347,9 @@ def load_library():
     L.rj_scan_records_format.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.c_int, ctypes.c_uint, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
     L.rj_scan_records_zip.restype = i64
     L.rj_scan_records_zip.argtypes = [vp, ctypes.POINTER(ZipColumn), ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_int, ctypes.c_uint, ctypes.c_int, u64, u64, vp, u64, vp, vp, vp]
+    L.rj_scan_records_format_time.restype = i64
+    L.rj_scan_records_format_time.argtypes = [vp, vp, vp, u64, vp, u64, cp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int, u64, u64, vp, u64, vp, vp,
+                                              ctypes.POINTER(_FormatTimeStats), vp]
     _lib = L
     return L
 
@@ -965,7 +972,8 @@ class Scan:
         below the unit: never truncated or rounded).  With stats=True also {"n_ok", "n_empty", "n_malformed", "n_range",
         "n_inexact"}.  records.time_buckets floors the values to buckets.  RejitError (RJ_BAD_ARGUMENT) for a bad index or row
         (naming the first bad row) and for a refused format (naming the byte offset).  The scan's spans, stats and
-        select_records stay as they were.  The inverse, %y %j %e %a %p, named zones, locales and leap seconds stay out."""
+        select_records stay as they were.  format_time_records is the inverse; %y %j %e %a %p, named zones, locales and leap
+        seconds stay out."""
         import torch
 
         t = text_tensor
@@ -1045,6 +1053,61 @@ class Scan:
         if total > out.numel():
             raise RejitError(-4, "format_records: the text has %d bytes, `out` %d" % (total, out.numel()))
         return out[:total], out_begin, out_end
+
+    def format_time_records(self, values, fmt, unit="s", status=None, indices=None, zone_minutes: int = 0, fill: int = 10, lead: int = 0, gap: int = 1, out=None,
+                            stream=None, stats=False):
+        """rj_scan_records_format_time: the inverse of parse_time_records -- a column of int64 instants (counts of `unit`, "s",
+        "ms", "us" or "ns", since 1970-01-01T00:00:00Z) written as text on the device under the strftime-style format `fmt`
+        (bytes or str, 1..64 bytes), laid out as format_records lays its rows out.  The directives are parse_time_records'
+        own, every one of a fixed width: %Y (4 digits), %m %d %H %M %S (2 each), %b (Jan..Dec), %f (the unit's fraction
+        digits: 3, 6 or 9; six zeros under "s"), %z (+hhmm of zone_minutes), %%; every other byte is a literal.  The instant
+        is floored toward minus infinity and shifted by `zone_minutes` (-1439..1439, one offset for the whole column).  Row j
+        is what Python's strftime writes for values[indices[j]] (or values[j]) -- %Y as isoformat's four digits --, or the
+        EMPTY row where `status` (uint8) is given and not PARSE_OK, or where the shifted year is outside 0001..9999.  Returns
+        (out_text, out_begin, out_end) as format_records does -- `gap` bytes of `fill` behind every row, `lead` in front;
+        without `out` one size query and an exact allocation, with `out` (contiguous uint8, 16-byte aligned) one call and
+        RejitError when it is too small --, with stats=True also {"n_ok", "n_null", "n_range"}.  RejitError (RJ_BAD_ARGUMENT)
+        for a bad index (naming the first bad row) and for a refused format (naming the byte offset).  The scan's spans,
+        stats and select_records stay as they were."""
+        import torch
+
+        v = values
+        assert v.is_contiguous() and v.is_cuda and v.dim() == 1 and v.dtype == torch.int64
+        if unit not in TIME_UNITS:
+            raise ValueError("format_time_records: unit is 's', 'ms', 'us' or 'ns', not %r" % (unit,))
+        fmt = fmt.encode("utf-8") if isinstance(fmt, str) else bytes(fmt)
+        n_values = int(v.numel())
+        if status is not None:
+            assert status.dtype == torch.uint8 and status.is_contiguous() and status.device == v.device and status.numel() == n_values
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == v.device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=v.device)   # (a non-null pointer: NULL means every value)
+        else:
+            k = n_values
+        st = torch.cuda.current_stream(v.device).cuda_stream if stream is None else stream
+        out_begin = torch.empty(k, dtype=torch.int64, device=v.device)
+        out_end = torch.empty(k, dtype=torch.int64, device=v.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        counts = _FormatTimeStats()
+
+        def call(buf, cap):
+            return int(_check(self._lib.rj_scan_records_format_time(self._h, ptr(v), ptr(status), n_values, ptr(indices), k, fmt, len(fmt), TIME_UNITS[unit],
+                                                                    int(zone_minutes), 0, int(fill), int(lead), int(gap), ptr(buf) if cap else None, cap,
+                                                                    ptr(out_begin), ptr(out_end), ctypes.byref(counts), ctypes.c_void_p(st))))
+        result = lambda text: (text, out_begin, out_end) + (({f: int(getattr(counts, f)) for f, _ in _FormatTimeStats._fields_},) if stats else ())
+        if out is None:
+            total = call(None, 0)
+            out = torch.empty(total, dtype=torch.uint8, device=v.device)
+            if total:
+                call(out, total)
+            return result(out)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == v.device
+        total = call(out, int(out.numel()))
+        if total > out.numel():
+            raise RejitError(-4, "format_time_records: the text has %d bytes, `out` %d" % (total, out.numel()))
+        return result(out[:total])
 
     def zip_records(self, columns, sep: bytes = b"", widths=None, pad: int = 32, fill: int = 10, lead: int = 0, gap: int = 1, out=None, stream=None,
                     flags: int = 0):

@@ -86,8 +86,10 @@ RJ_PACK_HD inline const char* format_error_text(int e) {
   }
 }
 
-// format[0, len) -> *out; on an error *at is the byte offset the message names
-inline int compile(const uint8_t* format, uint64_t len, Program* out, uint32_t* at) {
+// format[0, len) -> *out; on an error *at is the byte offset the message names.  `writing`: the format is compiled for
+// record_time_format.h, which writes rows -- the two refusals that only make sense when reading are lifted: a writer's %f has
+// a fixed width (nothing is greedy), and `%H:%M` is a fine thing to write (host code only, in both modes)
+inline int compile_mode(const uint8_t* format, uint64_t len, bool writing, Program* out, uint32_t* at) {
   Program p{};
   *at = 0;
   if (len == 0) return kFormatEmpty;
@@ -122,7 +124,7 @@ inline int compile(const uint8_t* format, uint64_t len, Program* out, uint32_t* 
         seen |= bit;
       }
     }
-    if (after_fraction && (op <= kFraction || (c >= '0' && c <= '9'))) {
+    if (!writing && after_fraction && (op <= kFraction || (c >= '0' && c <= '9'))) {
       *at = i;
       return kFormatGreedy;
     }
@@ -134,7 +136,7 @@ inline int compile(const uint8_t* format, uint64_t len, Program* out, uint32_t* 
     }
   }
   const uint32_t date = (1u << kYear) | (1u << kMonth) | (1u << kDay);
-  if ((seen & date) != date) {
+  if (!writing && (seen & date) != date) {
     *at = static_cast<uint32_t>(len);
     return kFormatNoDate;
   }
@@ -142,6 +144,7 @@ inline int compile(const uint8_t* format, uint64_t len, Program* out, uint32_t* 
   *out = p;
   return kFormatOk;
 }
+inline int compile(const uint8_t* format, uint64_t len, Program* out, uint32_t* at) { return compile_mode(format, len, false, out, at); }
 
 // ---------------------------------------------------------------------------------------------------------------- state
 enum Phase : uint32_t {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-D] [-Z] [-T FORMAT -w UNITS] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-D] [-Z] [-T FORMAT -w UNITS [-F OUTFORMAT]] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -60,6 +60,11 @@ answer on the GPU:
        line whose field N is missing, not in FORMAT, out of range (month 13, 30 February, a second of 60) or, under %f, has a
        non-zero fraction of a second is counted nowhere.  Only -p and -v go with it; a FORMAT the library refuses (an unknown directive, no %Y / %d /
        month, more than 64 bytes) is an error.  Exit status 0 when a line was counted, else 1
+  -F OUTFORMAT   with -T FORMAT -w UNITS: the bucket is printed as a TIMESTAMP under the strftime-style OUTFORMAT (the directives
+       of -T; `%Y-%m-%dT%H:%M` for requests per minute) instead of as a number of seconds -- "%7d %s".  The printed lines are
+       made on the device: rj_scan_records_format_time writes the buckets, rj_scan_records_format the counts (width 7),
+       rj_scan_records_zip puts them side by side with a space between, and that one text is the only download.  An
+       OUTFORMAT the library refuses is an error
 
 Exit status 0 when a line was selected, 1 when none was, 2 on errors -- grep's.  The engine's line breaks are \\n and \\r, and
 its dialect is the library's (include/rejit.h), not POSIX: for patterns that mean the same in both and cannot match across a
@@ -103,6 +108,10 @@ def main(argv):
     if "-w" in argv[:-1]:
         at = argv.index("-w")
         width, argv = argv[at + 1], argv[:at] + argv[at + 2:]
+    out_format = None
+    if "-F" in argv[:-1]:
+        at = argv.index("-F")
+        out_format, argv = os.fsencode(argv[at + 1]), argv[:at] + argv[at + 2:]
     matches_out, unique, byte_order, device_zip = "-o" in argv, "-u" in argv, "-b" in argv, "-Z" in argv
     device_text = "-D" in argv or device_zip
     argv = [a for a in argv if a not in ("-o", "-u", "-b", "-D", "-Z")]
@@ -112,7 +121,7 @@ def main(argv):
             unique and not matches_out and field is None) or (byte_order and not matches_out and field is None and "-p" not in flags) or (
             keys is not None and (repl is not None or top is not None or matches_out or unique or byte_order or agg is not None)) or (
             agg is not None and (not agg.isdigit() or int(agg) < 1 or not unique or field is None or matches_out)) or (
-            (time_format is None) != (width is None)) or (time_format is not None and (
+            (time_format is None) != (width is None)) or (out_format is not None and time_format is None) or (time_format is not None and (
                 not width.isdigit() or int(width) < 1 or field is None or matches_out or unique or byte_order or device_text or repl is not None
                 or keys is not None or agg is not None or top is not None or "-n" in flags or "-c" in flags)):
         sys.stderr.write(__doc__)
@@ -157,6 +166,16 @@ def main(argv):
             start, ok = records.time_buckets(values, status, int(width))
             buckets, counts = torch.unique(start[ok], return_counts=True)     # ascending; the only downloads
             counted = int(buckets.numel())
+            if out_format is not None and counted:
+                try:
+                    stamps = scan.format_time_records(buckets.contiguous(), out_format, unit="s")
+                except rejit_amd.RejitError as err:
+                    sys.stderr.write("linegrep_gpu: -F: %s\n" % err.message)
+                    return 2
+                printed, _, _ = scan.zip_records([scan.format_records(counts.contiguous()), stamps], sep=b" ", widths=[7, 0])
+                sys.stdout.flush()
+                sys.stdout.buffer.write(printed.cpu().numpy().tobytes())     # the only download
+                return 0
             sys.stdout.write("".join("%7d %d\n" % (c, b) for b, c in zip(buckets.cpu().tolist(), counts.cpu().tolist())))
         return 0 if counted else 1
     if keys is not None:
