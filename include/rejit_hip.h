@@ -677,6 +677,42 @@ int64_t rj_scan_records_format_time(rj_scan* scan, const uint64_t* d_value, cons
                                     uint64_t format_len, int unit, int zone_minutes, unsigned flags, int fill, uint64_t lead,
                                     uint64_t gap, void* d_out, uint64_t out_cap, uint64_t* d_out_begin, uint64_t* d_out_end,
                                     rj_format_time_stats* stats /* may be NULL */, void* hip_stream);
+/* The rows of a record table through a byte map and a drop set into a NEW packed device text (rejit_amd/csrc/
+ * record_translate.hip): `tr A-Z a-z`, `tr -d '\r'`, pandas str.lower / str.upper / str.translate,
+ * Arrow's ascii_lower / ascii_upper, Python's bytes.translate(table, delete) -- without a download, and in front of
+ * rj_scan_records_group / _sort / _lookup their case-insensitive forms.  The contract is rj_scan_records_pack's, word for word;
+ * only a row's bytes differ.  k, r(j), d_indices (any order, repeats allowed, non-NULL with n_indices == 0 is no rows), lead,
+ * gap and fill are the pack's.  Row j's bytes are
+ *     T(j) = bytes(text[rec_begin[r(j)], rec_end[r(j)])).translate(map, delete)       in Python's meaning:
+ * a byte in the drop set is removed -- judged on the SOURCE byte, before the map -- and every other byte b becomes map[b]; a
+ * NUL is an ordinary byte.  map: host, 256 bytes, NULL is the identity.  drop: host, 32 bytes = 256 bits, byte b is dropped
+ * when bit (b & 7) of drop[b >> 3] is set; NULL drops nothing.  Both travel as kernel arguments: no upload, no allocation.
+ * The layout is the pack's with len'(j) = |T(j)|:
+ *     ob(0) = lead, ob(j + 1) = ob(j) + len'(j) + gap, total = ob(k)                    (k == 0: total = lead)
+ *     d_out[ob(j), ob(j) + len'(j)) = T(j); every other byte of d_out[0, total) = fill
+ *     d_out_begin[j] = ob(j), d_out_end[j] = ob(j) + len'(j)                            (k uint64 each; either may be NULL)
+ * Returns total WHATEVER out_cap is and never writes at or beyond out_cap; d_out == NULL with out_cap == 0 is the size query
+ * (the tables and the stats are still written).  With total <= out_cap every byte of [0, total) and every table row is
+ * written exactly once, nothing has to be cleared first, nothing behind total or k is touched.  The scan lends scratch only:
+ * its span list, its stats and the state of its last rj_scan_records (rj_scan_records_select included) stay as they were.
+ * One synchronise per call.
+ * Refusals (RJ_BAD_ARGUMENT) are the pack's: a null argument, a table that is not 8-byte aligned, d_out not 16-byte aligned,
+ * fill outside 0..255, n + gap >= 2^42 or lead + k * (n + gap) >= 2^62 (also with gap 1), and an index >= n_records or a row
+ * without begin <= end <= n: the message's "row <j> " names the first bad j.  A refused call writes no output byte and no
+ * table row and is never led outside the text.  A d_out that overlaps the text is undefined, as elsewhere in the family.
+ * What stays out: UTF-8 case mapping, `tr -s` (that is rj_scan_records_replace with `x+`), multi-byte maps, in-place
+ * translation. */
+typedef struct {
+  uint64_t bytes_in;       /* source bytes of the k rows                          */
+  uint64_t bytes_dropped;  /* of those, bytes in the drop set                     */
+  uint64_t bytes_changed;  /* kept bytes b with map[b] != b                       */
+} rj_translate_stats;
+int64_t rj_scan_records_translate(rj_scan* scan, const void* d_text, uint64_t n, const uint64_t* d_rec_begin,
+                                  const uint64_t* d_rec_end, uint64_t n_records, const uint64_t* d_indices, uint64_t n_indices,
+                                  const uint8_t* map /* host, 256 bytes; NULL: identity */,
+                                  const uint8_t* drop /* host, 32 bytes = 256 bits; NULL: none */, int fill, uint64_t lead,
+                                  uint64_t gap, void* d_out, uint64_t out_cap, uint64_t* d_out_begin, uint64_t* d_out_end,
+                                  rj_translate_stats* stats /* may be NULL */, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

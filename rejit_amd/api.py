@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "record_time_format.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_time_format.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "record_time_format.hip", "record_translate.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_time_format.h", "record_translate.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -178,6 +178,10 @@ class _FormatTimeStats(ctypes.Structure):
     _fields_ = [("n_ok", ctypes.c_uint64), ("n_null", ctypes.c_uint64), ("n_range", ctypes.c_uint64)]
 
 
+class _TranslateStats(ctypes.Structure):
+    _fields_ = [("bytes_in", ctypes.c_uint64), ("bytes_dropped", ctypes.c_uint64), ("bytes_changed", ctypes.c_uint64)]
+
+
 class ZipColumn(ctypes.Structure):
     """rj_zip_column: one column of rj_scan_records_zip (64 bytes)"""
     _fields_ = [("d_text", ctypes.c_void_p), ("n", ctypes.c_uint64), ("d_rec_begin", ctypes.c_void_p), ("d_rec_end", ctypes.c_void_p),
@@ -225,7 +229,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip", "rj_scan_records_format_time"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip", "rj_scan_records_format_time", "rj_scan_records_translate"]
 
 
 def load_library():
@@ -350,6 +354,8 @@ def load_library():
     L.rj_scan_records_format_time.restype = i64
     L.rj_scan_records_format_time.argtypes = [vp, vp, vp, u64, vp, u64, cp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int, u64, u64, vp, u64, vp, vp,
                                               ctypes.POINTER(_FormatTimeStats), vp]
+    L.rj_scan_records_translate.restype = i64
+    L.rj_scan_records_translate.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, cp, cp, ctypes.c_int, u64, u64, vp, u64, vp, vp, ctypes.POINTER(_TranslateStats), vp]
     _lib = L
     return L
 
@@ -709,6 +715,68 @@ class Scan:
         if total > out.numel():
             raise RejitError(-4, "pack_records: the packed text has %d bytes, `out` %d" % (total, out.numel()))
         return out[:total], out_begin, out_end
+
+    def translate_records(self, text_tensor, rec_begin, rec_end, table=None, delete: bytes = b"", indices=None, fill=None, lead: int = 0, gap: int = 1,
+                          out=None, stream=None, stats=False):
+        """rj_scan_records_translate: pack_records in which every packed record goes through Python's
+        bytes.translate(table, delete) on the device -- `tr A-Z a-z`, `tr -d '\\r'`, str.lower / str.upper / str.translate
+        over a column.  `table`: 256 bytes (records.ASCII_LOWER, records.ASCII_UPPER, records.byte_map), None is the identity;
+        `delete`: the bytes to remove, as bytes or as records.drop_set's 32-byte set -- judged on the source byte, before the
+        table.  indices, fill (None: the batch separator), lead, gap, out and the returned (out_text, out_begin, out_end) are
+        pack_records': without `out` ONE size query and an exact allocation, with `out` (contiguous uint8, 16-byte aligned)
+        one call and RejitError when it is too small.  stats=True adds {"bytes_in", "bytes_dropped", "bytes_changed"}.  In
+        front of group_records / sort_records / lookup_records it makes them `uniq -ci`, `sort -f` and a case-insensitive
+        join.  The scan's spans, stats and select_records stay as they were."""
+        import torch
+        from . import records as _records
+
+        t = text_tensor
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        n_records = int(rec_begin.numel())
+        for x in (rec_begin, rec_end):
+            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
+        if table is not None:
+            table = bytes(table)
+            if len(table) != 256:
+                raise ValueError("translate_records: table has %d bytes, not 256" % len(table))
+        drop = None
+        if isinstance(delete, _records.DropSet):
+            drop = bytes(delete)
+        elif delete:
+            drop = bytes(_records.drop_set(delete))
+        if fill is None:
+            fill = self.program.batch_separator()
+            if fill < 0:
+                raise RejitError(-4, "translate_records: the pattern has no batch separator (it is matched text by text): pass fill")
+        if indices is not None:
+            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
+            k = int(indices.numel())
+            if k == 0:
+                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
+        else:
+            k = n_records
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        out_begin = torch.empty(k, dtype=torch.int64, device=t.device)
+        out_end = torch.empty(k, dtype=torch.int64, device=t.device)
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+        counts = _TranslateStats()
+
+        def call(buf, cap):
+            return int(_check(self._lib.rj_scan_records_translate(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k,
+                                                                  table, drop, int(fill), int(lead), int(gap), ptr(buf) if cap else None, cap, ptr(out_begin),
+                                                                  ptr(out_end), ctypes.byref(counts) if stats else None, ctypes.c_void_p(st))))
+        result = lambda text: (text, out_begin, out_end) + (({f: int(getattr(counts, f)) for f, _ in _TranslateStats._fields_},) if stats else ())
+        if out is None:
+            total = call(None, 0)
+            out = torch.empty(total, dtype=torch.uint8, device=t.device)
+            if total:
+                call(out, total)
+            return result(out)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == t.device
+        total = call(out, int(out.numel()))
+        if total > out.numel():
+            raise RejitError(-4, "translate_records: the translated text has %d bytes, `out` %d" % (total, out.numel()))
+        return result(out[:total])
 
     def replace_records(self, text_tensor, rec_begin, rec_end, result: RecordsResult, repl: bytes, indices=None, fill=None, lead: int = 0,
                         gap: int = 1, out=None, stream=None):

@@ -179,6 +179,9 @@ struct rj_scan {
   // rj_scan_records_zip (record_zip.hip) shares the summary, the look-back words and rec_pack_begin; rec_zip_stage: the rows'
   // lengths (8 bytes per row), then the 16 bytes per piece between its resolve and its emit
   rejit_amd::DeviceBuffer rec_zip_stage;
+  // rj_scan_records_translate (record_translate.hip) shares the summary and the look-back words; rec_translate_stage: the rows'
+  // places in its virtual stream (8 bytes per row), then the kept bytes before each unit of slabs (8 bytes per unit)
+  rejit_amd::DeviceBuffer rec_translate_stage;
   unsigned long long* rec_host = nullptr;
   const uint32_t* rec_select_counts = nullptr;
   uint64_t rec_n = 0;

@@ -181,3 +181,32 @@ def time_buckets(values, status, width: int):
         raise ValueError("time_buckets: width is a positive number of units, not %r" % (width,))
     start = torch.div(values, width, rounding_mode="floor") * width
     return start, status == 0
+
+
+# ---- byte tables for Scan.translate_records (rj_scan_records_translate): bytes plumbing only
+class DropSet(bytes):
+    """the 32-byte (256-bit) drop set of rj_scan_records_translate: byte b is dropped when bit (b & 7) of self[b >> 3] is set
+    (a type of its own, so that translate_records can tell it from the bytes to delete)"""
+
+
+def byte_map(src: bytes = b"", dst: bytes = b"") -> bytes:
+    """The 256-byte table that maps src[i] to dst[i] and every other byte to itself (bytes.maketrans with one rule more: where
+    a byte stands in src twice, the later pair wins)."""
+    if len(src) != len(dst):
+        raise ValueError("byte_map: src has %d bytes, dst %d" % (len(src), len(dst)))
+    table = bytearray(range(256))
+    for a, b in zip(src, dst):
+        table[a] = b
+    return bytes(table)
+
+
+def drop_set(delete: bytes) -> DropSet:
+    """The drop set that holds the bytes of `delete`."""
+    bits = bytearray(32)
+    for b in delete:
+        bits[b >> 3] |= 1 << (b & 7)
+    return DropSet(bits)
+
+
+ASCII_LOWER = byte_map(bytes(range(0x41, 0x5B)), bytes(range(0x61, 0x7B)))   # str.lower over ASCII, Arrow's ascii_lower
+ASCII_UPPER = byte_map(bytes(range(0x61, 0x7B)), bytes(range(0x41, 0x5B)))   # str.upper over ASCII, Arrow's ascii_upper

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-D] [-Z] [-T FORMAT -w UNITS [-F OUTFORMAT]] -- count, number or print the lines of FILE in which a match of PATTERN
+"""linegrep_gpu.py FILE PATTERN [-c] [-v] [-n] [-p] [-s WITH] [-o] [-f N] [-u [-t K] [-a M | -A M]] [-b] [-k KEYS] [-i] [-D] [-Z] [-T FORMAT -w UNITS [-F OUTFORMAT]] -- count, number or print the lines of FILE in which a match of PATTERN
 begins, the way `grep -E -c` / `grep -E -n | cut -d: -f1` / plain `grep -E` do, with everything between the upload and the
 answer on the GPU:
 
@@ -44,6 +44,11 @@ answer on the GPU:
        in a line break, as `grep -f` reads it), and rj_scan_records_lookup looks the lines or the fields up in them on the
        device: only the count (-c), the numbers (-n) or the packed lines (-p) come back.  Beside -k only -c, -n, -p, -v and
        -f N are allowed.
+  -i   ignore ASCII case: the file's lines are lowered ONCE on the device (rj_scan_records_translate with the A-Z -> a-z table:
+       a new device text with its own line table, no download) before the scan and before any grouping or sorting, so a
+       lower-case PATTERN is `grep -i`.  With -c / -n / -p the selected row numbers index the original table and the ORIGINAL
+       lines are printed; with -u it is `uniq -ci`, with -b `sort -f` (ties aside), and every other option that prints parts of
+       lines (-o, -f N, -s WITH) prints them lowered.  Not together with -k
   -D   numbers as text from the device: with -n the 1-based line numbers, with -a M / -A M the sums, are written as decimal
        text by rj_scan_records_format -- str(int) / repr(float), byte for byte -- and only that packed text is downloaded,
        not the values; the output is the output without -D
@@ -112,14 +117,14 @@ def main(argv):
     if "-F" in argv[:-1]:
         at = argv.index("-F")
         out_format, argv = os.fsencode(argv[at + 1]), argv[:at] + argv[at + 2:]
-    matches_out, unique, byte_order, device_zip = "-o" in argv, "-u" in argv, "-b" in argv, "-Z" in argv
+    matches_out, unique, byte_order, device_zip, fold = "-o" in argv, "-u" in argv, "-b" in argv, "-Z" in argv, "-i" in argv
     device_text = "-D" in argv or device_zip
-    argv = [a for a in argv if a not in ("-o", "-u", "-b", "-D", "-Z")]
+    argv = [a for a in argv if a not in ("-o", "-u", "-b", "-D", "-Z", "-i")]
     flags = [a for a in argv if a in ("-c", "-v", "-n", "-p")]
     rest = [a for a in argv if a not in ("-c", "-v", "-n", "-p")]
     if len(rest) != 2 or (field is not None and (not field.isdigit() or int(field) < 1)) or (top is not None and (not top.isdigit() or not unique)) or (
             unique and not matches_out and field is None) or (byte_order and not matches_out and field is None and "-p" not in flags) or (
-            keys is not None and (repl is not None or top is not None or matches_out or unique or byte_order or agg is not None)) or (
+            keys is not None and (repl is not None or top is not None or matches_out or unique or byte_order or agg is not None or fold)) or (
             agg is not None and (not agg.isdigit() or int(agg) < 1 or not unique or field is None or matches_out)) or (
             (time_format is None) != (width is None)) or (out_format is not None and time_format is None) or (time_format is not None and (
                 not width.isdigit() or int(width) < 1 or field is None or matches_out or unique or byte_order or device_text or repl is not None
@@ -149,6 +154,9 @@ def main(argv):
     if data[-1] in (10, 13):                                         # `^` also matches behind the file's last line break: not a line
         begins, ends = begins[:-1].contiguous(), ends[:-1].contiguous()
     scan = rejit_amd.Scan(rejit_amd.Program(pattern))
+    original = (text, begins, ends)
+    if fold:                                                         # the lowered lines: a new device text, the same row numbers
+        text, begins, ends = scan.translate_records(text, begins, ends, table=records.ASCII_LOWER, fill=10, lead=0, gap=1)
     result = scan.run_records(text, begins, ends)
     selected = result.n_records - result.n_matching if invert else result.n_matching
     if time_format is not None:
@@ -288,6 +296,8 @@ def main(argv):
             lines = scan.select_records(invert=invert)
             if byte_order:
                 lines = lines[scan.sort_records(text, begins, ends, indices=lines)].contiguous()
+            else:
+                text, begins, ends = original                        # (-i: the rows' numbers are the original table's)
             packed, _, _ = scan.pack_records(text, begins, ends, indices=lines, fill=10, lead=0, gap=1)
             sys.stdout.flush()
             sys.stdout.buffer.write(packed.cpu().numpy().tobytes())   # the only download besides the summary
