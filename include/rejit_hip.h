@@ -713,6 +713,58 @@ int64_t rj_scan_records_translate(rj_scan* scan, const void* d_text, uint64_t n,
                                   const uint8_t* drop /* host, 32 bytes = 256 bits; NULL: none */, int fill, uint64_t lead,
                                   uint64_t gap, void* d_out, uint64_t out_cap, uint64_t* d_out_begin, uint64_t* d_out_end,
                                   rj_translate_stats* stats /* may be NULL */, void* hip_stream);
+/* The rows and fields of a device-resident CSV text with QUOTED fields (RFC 4180: the quote byte around a field, doubled inside
+ * it) as record tables (rejit_amd/csrc/record_csv.hip) -- the family's front door for texts in which
+ * a field may hold the delimiter or a line break.  Let ins(p) be the parity of the quote bytes in text[0, p) (quote == -1:
+ * always 0).  Byte p is STRUCTURAL when ins(p) == 0 and it is the delimiter or \n.  Fields are the stretches between
+ * structural bytes; a \n also ends a row; a \r directly before a row-ending \n belongs to neither.  A text that does not end
+ * in a structural \n has a last row that ends at n, one that does has no extra row, n == 0 has no rows; every row has at
+ * least one field (an empty line is one empty field).  For the raw field [fb, fe):
+ *     begin = fb + 1 when fb < fe and text[fb] is the quote, else fb
+ *     end   = fe - 1 when fe > begin, text[fe - 1] is the quote and the field is not the last one of a text with ins(n) == 1,
+ *             else fe
+ * and its flags are the OR over its bytes of
+ *     RJ_CSV_BAD_QUOTE  a quote at p with ins(p) == 0 that is neither at fb nor directly behind a quote
+ *     RJ_CSV_ESCAPED    a quote at p with ins(p) == 0, not at fb, directly behind a quote (the second byte of a `""`)
+ *     RJ_CSV_BAD_CLOSE  a quote at p with ins(p) == 1 not followed by the text's end, the delimiter, \n, \r\n or a quote
+ *     RJ_CSV_BARE_CR    a \r with ins(p) == 0 that is not followed by \n
+ *     RJ_CSV_OPEN       on the last field when ins(n) == 1
+ * If no field carries an RJ_CSV_MALFORMED flag, rows and values are those of Python's csv.reader(strict=True) exactly (a
+ * field's value: its bytes, `""` read as `"` where it is ESCAPED; an empty line is ['']); otherwise every row before the
+ * first flagged row is.  On flagged fields and behind them the rule above is the meaning.  With quote == -1 and no \r other
+ * than in \r\n the fields are line.split(delimiter) of the lines.
+ *     d_row_first[0] = 0, d_row_first[r + 1] = d_row_first[r] + (fields of row r)        (row_cap + 1 uint64: Arrow's offsets)
+ *     d_row_begin[r], d_row_end[r]: the raw row without its line break                   (row_cap uint64 each)
+ *     d_field_begin[f], d_field_end[f], d_field_flags[f]: field f in text order          (field_cap each; the flags 4 bytes)
+ * Rows and fields ascend and do not overlap: each pair is a record table for every other call of the family.  Every table
+ * may be NULL and is then not written.  Returns n_fields WHATEVER the caps are; never writes a row at or beyond row_cap or
+ * a field at or beyond field_cap; all tables NULL with both caps 0 is the size query, and `stats` (host, required) is complete
+ * in it too.  With n_rows <= row_cap and n_fields <= field_cap every entry below the counts is written exactly once as the
+ * caller sees it (d_field_flags is cleared by the call), nothing has to be cleared first, nothing behind the counts is
+ * touched.  The scan lends scratch only: its span list, its stats and the state of its last rj_scan_records stay as they
+ * were.  One synchronise per call.  stats.first_bad: the offset of the first byte that raised BAD_QUOTE, BAD_CLOSE or
+ * BARE_CR, n for a text that is only OPEN, UINT64_MAX when nothing is malformed.
+ * Refusals (RJ_BAD_ARGUMENT, no byte written): a null scan, a null text with n > 0, stats == NULL, a table that is not 8-byte
+ * aligned (the flags: 4-byte), delimiter outside 0..255, quote outside -1..255, delimiter or quote equal to \n or \r,
+ * delimiter equal to quote, n >= 2^42.
+ * What stays out: a text range other than [0, n), multi-byte delimiters, backslash escapes, skipinitialspace, comment lines,
+ * skipping blank lines, header handling (drop row 0 with `indices`), type inference, and unescaping inside this call (pack
+ * the fields, then rj_scan_records_replace `""` by `"`). */
+typedef struct rj_csv_stats {
+  uint64_t n_rows, n_fields;
+  uint64_t n_quoted;     /* fields whose first raw byte is the quote byte                */
+  uint64_t n_escapes;    /* doubled quotes inside quoted fields (events, not fields)     */
+  uint64_t n_bad_quote, n_bad_close, n_bare_cr;   /* events                              */
+  uint64_t open_at_end;  /* 1: the text ends inside quotes                               */
+  uint64_t first_bad;    /* text offset of the first offending byte, UINT64_MAX: none    */
+} rj_csv_stats;
+enum { RJ_CSV_ESCAPED = 1, RJ_CSV_BAD_QUOTE = 2, RJ_CSV_BAD_CLOSE = 4, RJ_CSV_BARE_CR = 8, RJ_CSV_OPEN = 16 };
+#define RJ_CSV_MALFORMED (RJ_CSV_BAD_QUOTE | RJ_CSV_BAD_CLOSE | RJ_CSV_BARE_CR | RJ_CSV_OPEN)
+int64_t rj_scan_records_csv(rj_scan* scan, const void* d_text, uint64_t n, int delimiter, int quote /* -1: none */,
+                            uint64_t* d_row_first /* row_cap + 1 */, uint64_t* d_row_begin, uint64_t* d_row_end /* row_cap each */,
+                            uint64_t row_cap, uint64_t* d_field_begin, uint64_t* d_field_end,
+                            uint32_t* d_field_flags /* field_cap each */, uint64_t field_cap, rj_csv_stats* stats /* host, required */,
+                            void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

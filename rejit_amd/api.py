@@ -8,12 +8,16 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "record_time_format.hip", "record_translate.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_time_format.h", "record_translate.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "record_time_format.hip", "record_translate.hip", "record_csv.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_time_format.h", "record_translate.h", "record_csv.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+
+
+def _raise(e):
+    raise e
 
 
 class RejitError(RuntimeError):
@@ -182,6 +186,28 @@ class _TranslateStats(ctypes.Structure):
     _fields_ = [("bytes_in", ctypes.c_uint64), ("bytes_dropped", ctypes.c_uint64), ("bytes_changed", ctypes.c_uint64)]
 
 
+class _CsvStats(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("n_rows", "n_fields", "n_quoted", "n_escapes", "n_bad_quote", "n_bad_close", "n_bare_cr", "open_at_end",
+                                               "first_bad")]
+
+
+class CsvResult:
+    """What Scan.csv_records returns: the tables of rj_scan_records_csv as tensors on the text's device -- row_first (int64,
+    n_rows + 1), row_begin / row_end (int64, n_rows; None with rows=False), field_begin / field_end (int64, n_fields),
+    field_flags (int32, n_fields: the CSV_* bits) -- and stats, rj_csv_stats as a dict (first_bad: None when nothing is
+    malformed)."""
+
+    def __init__(self, row_first, row_begin, row_end, field_begin, field_end, field_flags, stats):
+        self.row_first, self.row_begin, self.row_end = row_first, row_begin, row_end
+        self.field_begin, self.field_end, self.field_flags = field_begin, field_end, field_flags
+        self.stats = stats
+        self.n_rows, self.n_fields = stats["n_rows"], stats["n_fields"]
+
+
+CSV_ESCAPED, CSV_BAD_QUOTE, CSV_BAD_CLOSE, CSV_BARE_CR, CSV_OPEN = 1, 2, 4, 8, 16
+CSV_MALFORMED = CSV_BAD_QUOTE | CSV_BAD_CLOSE | CSV_BARE_CR | CSV_OPEN
+
+
 class ZipColumn(ctypes.Structure):
     """rj_zip_column: one column of rj_scan_records_zip (64 bytes)"""
     _fields_ = [("d_text", ctypes.c_void_p), ("n", ctypes.c_uint64), ("d_rec_begin", ctypes.c_void_p), ("d_rec_end", ctypes.c_void_p),
@@ -229,7 +255,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip", "rj_scan_records_format_time", "rj_scan_records_translate"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip", "rj_scan_records_format_time", "rj_scan_records_translate", "rj_scan_records_csv"]
 
 
 def load_library():
@@ -356,6 +382,8 @@ def load_library():
                                               ctypes.POINTER(_FormatTimeStats), vp]
     L.rj_scan_records_translate.restype = i64
     L.rj_scan_records_translate.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, cp, cp, ctypes.c_int, u64, u64, vp, u64, vp, vp, ctypes.POINTER(_TranslateStats), vp]
+    L.rj_scan_records_csv.restype = i64
+    L.rj_scan_records_csv.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, vp, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(_CsvStats), vp]
     _lib = L
     return L
 
@@ -777,6 +805,47 @@ class Scan:
         if total > out.numel():
             raise RejitError(-4, "translate_records: the translated text has %d bytes, `out` %d" % (total, out.numel()))
         return result(out[:total])
+
+    def csv_records(self, text_tensor, delimiter: bytes = b",", quote=b'"', rows: bool = True, stream=None, row_cap: Optional[int] = None,
+                    field_cap: Optional[int] = None) -> CsvResult:
+        """rj_scan_records_csv: the rows and fields of the CSV text `text_tensor` (contiguous uint8 on the GPU) with quoted fields
+        -- delimiters and line breaks inside quotes are data, `""` inside a quoted field is flagged CSV_ESCAPED (records.csv_values
+        unescapes), malformed quoting is flagged per field, never guessed.  delimiter / quote: one byte each (or an int); quote=None:
+        no quoting.  One size query, then the fill into exact allocations; with row_cap and field_cap both given the fill alone,
+        and RejitError when either was too small.  rows=False leaves row_begin / row_end out.  Returns a CsvResult; every
+        (begin, end) pair of it is a record table for the other record calls.  The scan's spans, stats and select_records stay
+        as they were."""
+        import torch
+
+        t = text_tensor
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        byte = lambda x, name: x if isinstance(x, int) else (bytes(x)[0] if len(bytes(x)) == 1 else _raise(ValueError("csv_records: %s is not one byte" % name)))
+        d = byte(delimiter, "delimiter")
+        q = -1 if quote is None else byte(quote, "quote")
+        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        cs = _CsvStats()
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+
+        def call(tables, rcap, fcap):
+            rf, rb, re, fb, fe, ff = tables
+            return int(_check(self._lib.rj_scan_records_csv(self._h, ptr(t), int(t.numel()), d, q, ptr(rf), ptr(rb), ptr(re), rcap, ptr(fb), ptr(fe), ptr(ff), fcap,
+                                                            ctypes.byref(cs), ctypes.c_void_p(st))))
+        if row_cap is None or field_cap is None:
+            call((None,) * 6, 0, 0)
+            row_cap, field_cap = int(cs.n_rows), int(cs.n_fields)
+        row_cap, field_cap = int(row_cap), int(field_cap)
+        i64 = lambda k: torch.empty(k, dtype=torch.int64, device=t.device)
+        tables = (i64(row_cap + 1), i64(row_cap) if rows else None, i64(row_cap) if rows else None, i64(field_cap), i64(field_cap),
+                  torch.empty(field_cap, dtype=torch.int32, device=t.device))
+        call(tables, row_cap, field_cap)
+        n_rows, n_fields = int(cs.n_rows), int(cs.n_fields)
+        if n_rows > row_cap or n_fields > field_cap:
+            raise RejitError(-4, "csv_records: the text has %d rows and %d fields, the caps were %d and %d" % (n_rows, n_fields, row_cap, field_cap))
+        stats = {f: int(getattr(cs, f)) for f, _ in _CsvStats._fields_}
+        if stats["first_bad"] == (1 << 64) - 1:
+            stats["first_bad"] = None
+        rf, rb, re, fb, fe, ff = tables
+        return CsvResult(rf[:n_rows + 1], rb[:n_rows] if rows else None, re[:n_rows] if rows else None, fb[:n_fields], fe[:n_fields], ff[:n_fields], stats)
 
     def replace_records(self, text_tensor, rec_begin, rec_end, result: RecordsResult, repl: bytes, indices=None, fill=None, lead: int = 0,
                         gap: int = 1, out=None, stream=None):

@@ -1340,6 +1340,7 @@ void rj_scan_destroy(rj_scan* s) {
   if (s->small_text) (void)hipHostFree(s->small_text);
   if (s->gx_host) (void)hipHostFree(s->gx_host);
   if (s->rec_host) (void)hipHostFree(s->rec_host);
+  if (s->rec_csv_host) (void)hipHostFree(s->rec_csv_host);
   for (auto& e : s->ev)
     if (e) (void)hipEventDestroy(e);
   if (s->own_stream) (void)hipStreamDestroy(s->own_stream);

@@ -182,6 +182,10 @@ struct rj_scan {
   // rj_scan_records_translate (record_translate.hip) shares the summary and the look-back words; rec_translate_stage: the rows'
   // places in its virtual stream (8 bytes per row), then the kept bytes before each unit of slabs (8 bytes per unit)
   rejit_amd::DeviceBuffer rec_translate_stage;
+  // rj_scan_records_csv (record_csv.hip) shares nothing with the others: rec_csv_stage holds its stats words, the spans'
+  // summaries and their entries; rec_csv_host: the pinned copy of the stats words
+  rejit_amd::DeviceBuffer rec_csv_stage;
+  unsigned long long* rec_csv_host = nullptr;
   unsigned long long* rec_host = nullptr;
   const uint32_t* rec_select_counts = nullptr;
   uint64_t rec_n = 0;

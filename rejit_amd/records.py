@@ -210,3 +210,54 @@ def drop_set(delete: bytes) -> DropSet:
 
 ASCII_LOWER = byte_map(bytes(range(0x41, 0x5B)), bytes(range(0x61, 0x7B)))   # str.lower over ASCII, Arrow's ascii_lower
 ASCII_UPPER = byte_map(bytes(range(0x61, 0x7B)), bytes(range(0x41, 0x5B)))   # str.upper over ASCII, Arrow's ascii_upper
+
+
+# ---- the tables of Scan.csv_records (rj_scan_records_csv): torch plumbing only
+def csv_column(row_first, c: int):
+    """(field_index, present): the number of the field in column c (0-based; negative: counted from the row's end) of every
+    row of Scan.csv_records' row_first -- an int64 tensor of n_rows entries, the `indices` of every other record call over
+    (field_begin, field_end) -- and a bool tensor that says which rows have such a column.  A ragged row that lacks it is
+    not present, and its index is its own first field's (every row has one), so that the index stays valid: leave those rows
+    out with `present`."""
+    import torch
+
+    lo, hi = row_first[:-1], row_first[1:]
+    at = lo + c if c >= 0 else hi + c
+    present = (at >= lo) & (at < hi)
+    return torch.where(present, at, lo).contiguous(), present
+
+
+def csv_bad_rows(row_first, field_flags):
+    """A bool tensor of n_rows entries: does the row hold a field with a CSV_MALFORMED flag (its values are the rule's, not a
+    CSV reader's: include/rejit_hip.h)."""
+    import torch
+    from .api import CSV_MALFORMED
+
+    bad = ((field_flags & CSV_MALFORMED) != 0).to(torch.int64)
+    upto = torch.cat([torch.zeros(1, dtype=torch.int64, device=bad.device), torch.cumsum(bad, 0)])
+    return upto[row_first[1:]] > upto[row_first[:-1]]
+
+
+def csv_values(scan, text, field_begin, field_end, field_flags, indices=None, quote: bytes = b'"', fill: int = 10):
+    """(out_text, out_begin, out_end): the VALUES of the fields of Scan.csv_records -- all of them, or those `indices` names
+    (csv_column) -- as a packed device text with its record table, a doubled quote read as one.  When no chosen field is
+    CSV_ESCAPED that is scan.pack_records; otherwise the pack, then a scan for the doubled quote over the PACKED text, then
+    replace_records with the single one.  (Never a scan of the original text: in a field whose value begins with a quote (three quote bytes, then `a`, then one) the leftmost match would pair the
+    opening quote with the first byte of the escape and cross the field's begin; in the packed text the separator `fill`,
+    which must not be the quote, makes the fields independent.)  `scan` lends scratch only."""
+    import torch
+    from .api import CSV_ESCAPED
+
+    chosen = field_flags if indices is None else field_flags[indices]
+    packed, ob, oe = scan.pack_records(text, field_begin, field_end, indices=indices, fill=fill)
+    if not bool(((chosen & CSV_ESCAPED) != 0).any()):
+        return packed, ob, oe
+    q = bytes(quote)
+    assert len(q) == 1 and q[0] != fill
+    finder = getattr(scan, "_csv_unescape", None)
+    if finder is None or finder[0] != q:
+        lit = b"\\x%02x" % q[0]
+        finder = (q, Scan(Program(lit + lit)))
+        scan._csv_unescape = finder
+    found = finder[1].run_records(packed, ob, oe)
+    return finder[1].replace_records(packed, ob, oe, found, q, fill=fill)
