@@ -53,9 +53,11 @@ namespace {
 
 constexpr uint64_t kBlock = 2048;     // bytes a wave takes per iteration: 64 lanes x 2 pieces of 16 B
 constexpr uint32_t kPieceB = 1024;    // a lane's piece B begins this far behind its piece A
-// Capture (ExactShape): a wave keeps the raw bytes of the last two blocks in LDS -- a block's 2 KiB in text order and, behind
-// them, the first 8 bytes of the block that follows -- and a candidate takes its 8 bytes from there when it enters the ring.
-constexpr uint32_t kStashWords = (2048 + 16) / 4;
+// Capture (ExactShape): a wave keeps the raw bytes of the last two blocks in LDS, in text order, as ONE ring of 4 KiB -- the
+// span's block i in slot i & 1 --, and a candidate takes its 8 bytes from there when it enters the ring of candidates: the
+// bytes behind a block are the first bytes of the other slot, whichever way round (a window's three words wrap at 4 KiB).
+constexpr uint32_t kStashSlotWords = 2048 / 4;
+constexpr uint32_t kStashBytes = 2 * 2048;
 #ifndef RJ_PC_RING
 #define RJ_PC_RING 256
 #endif
@@ -72,14 +74,26 @@ struct Raw {
 };
 
 // (a uniform base and a 32-bit lane offset: the load takes its address from a scalar pair + one register, no 64-bit
-// pointer per lane is kept alive across the loop)
-__device__ __forceinline__ void load_block(const uint8_t* block, uint32_t lane_off, Raw& r) {
-  r.a = stream_load16(block + lane_off);
-  r.b = stream_load16(block + lane_off + kPieceB);
+// pointer per lane is kept alive across the loop.  The empty statement keeps the base a scalar of its own: without it the
+// loop's loads had `text + lane_off` hoisted into a register pair and the block's offset added per lane, a 64-bit vector
+// add and three scalar instructions per load pair.  Behind such a statement a pointer's address space is no longer known
+// to the compiler: the text is device memory, and the base says so.)
+// (extra: a constant added behind the statement, for the load's immediate offset)
+__device__ __forceinline__ void load_block(const uint8_t* block, uint32_t lane_off, Raw& r, uint32_t extra = 0) {
+  typedef const __attribute__((address_space(1))) uint8_t* GlobalBytes;
+  GlobalBytes base = (GlobalBytes)block;
+  asm("" : "+s"(base));
+  asm volatile("" : "+v"(lane_off));   // (the offset's extension to 64 bits stays beside the load, which then takes it as 32 bits)
+  r.a = stream_load16((const uint8_t*)(base + lane_off + extra));
+  r.b = stream_load16((const uint8_t*)(base + lane_off + extra + kPieceB));
 }
 
 __device__ __forceinline__ uint32_t guarded_dword(const uint8_t* text, uint64_t n, uint64_t at) {
   uint32_t v = 0;
+  if (at + 4 <= n) {   // (whole: all but the text's last few bytes)
+    __builtin_memcpy(&v, text + at, 4);
+    return v;
+  }
 #pragma unroll
   for (int k = 0; k < 4; k++)
     if (at + k < n) v |= static_cast<uint32_t>(text[at + k]) << (8 * k);
@@ -88,7 +102,9 @@ __device__ __forceinline__ uint32_t guarded_dword(const uint8_t* text, uint64_t 
 
 // Window positions of the lane's two pieces that lie within one code of a base: bit 2k = byte k of piece A, bit 2k + 1 =
 // byte k of piece B.  ta / tb: the codes of the pieces; ha / hb: the codes of the 8 bytes behind each of them (bits 0..15).
-template <int NB>
+// COLD: a call outside the streaming loop (the guarded blocks at the end of the text), which extracts the pick indices where it
+// uses them; the loop's calls share sixteen indices extracted once per wave.
+template <int NB, bool COLD>
 __device__ __forceinline__ uint32_t plane_test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const PlaneCountParams& a) {
   constexpr uint32_t kEven = 0x55555555u;
   const uint32_t L = (ta & kEven) | ((tb << 1) & ~kEven);
@@ -117,8 +133,10 @@ __device__ __forceinline__ uint32_t plane_test(uint32_t ta, uint32_t tb, uint32_
   register uint32_t n2 asm("v54") = ~Ln & Hn;
   register uint32_t n3 asm("v55") = Ln & Hn;
   uint32_t codes = ~a.mask_bits;   // (mask bit set = that bit of the code is 0)
-  asm volatile("" : "+s"(codes));
-  auto code = [&](int b, int i) { return (codes >> (16 * b + 2 * i)) & 3u; };   // (wave-uniform: a scalar bit-field extract)
+  if (COLD) asm volatile("" : "+s"(codes));   // (not hoisted: sixteen more scalar registers held across that loop spilled two)
+  // (wave-uniform launch constants: sixteen scalar bit-field extracts, made once per wave and kept in scalar registers across the
+  // streaming loop)
+  auto code = [&](int b, int i) { return (codes >> (16 * b + 2 * i)) & 3u; };
   uint32_t E[8][NB], Z[NB], O[NB];
 #pragma unroll
   for (int half = 0; half < 2; half++) {
@@ -250,7 +268,8 @@ struct ExactShape {
   __device__ static __forceinline__ const PlaneCountParams& common(const Args& g) { return g; }
   __device__ static __forceinline__ uint32_t lmax(const Args&) { return 8u; }
   __device__ static __forceinline__ uint32_t offset_of(const Args&, const uint32_t*, uint32_t) { return 0u; }
-  __device__ static __forceinline__ uint32_t test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const Args& g) { return plane_test<NB>(ta, tb, ha, hb, g); }
+  template <bool COLD = false>
+  __device__ static __forceinline__ uint32_t test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const Args& g) { return plane_test<NB, COLD>(ta, tb, ha, hb, g); }
   // the patterns that match the 8 bytes at window position `pos` (the scan does not clip: windows before the range, or
   // with bytes beyond the end of the text, are dropped here)
   __device__ static __forceinline__ void classify(const Args& a, const uint32_t* table, uint64_t pos, bool have, uint32_t& mask, Lens&) {
@@ -284,7 +303,8 @@ struct ListShape {
   __device__ static __forceinline__ const PlaneCountParams& common(const Args& g) { return g.c; }
   __device__ static __forceinline__ uint32_t lmax(const Args&) { return 8u; }
   __device__ static __forceinline__ uint32_t offset_of(const Args&, const uint32_t*, uint32_t) { return 0u; }
-  __device__ static __forceinline__ uint32_t test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const Args& g) { return plane_test<NB>(ta, tb, ha, hb, g.c); }
+  template <bool COLD = false>
+  __device__ static __forceinline__ uint32_t test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const Args& g) { return plane_test<NB, COLD>(ta, tb, ha, hb, g.c); }
   __device__ static __forceinline__ void classify(const Args&, const uint32_t*, uint64_t, bool, uint32_t& mask, Lens&) { mask = 0; }
 };
 
@@ -380,6 +400,7 @@ struct GeneralShape {
   __device__ static __forceinline__ uint32_t offset_of(const Args&, const uint32_t* blob, uint32_t p) {
     return reinterpret_cast<const ClassifyDesc*>(blob)[p].win_offset;
   }
+  template <bool COLD = false>
   __device__ static __forceinline__ uint32_t test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const Args& g) { return general_test<TOL>(ta, tb, ha, hb, g); }
   // per pattern: the start s = w - its window offset inside the own range, the window inside the text, one of its windows
   // matches exactly -- then its automaton from s (classify_shared_general's steps 1 and 2, for 64 candidates at a time)
@@ -448,6 +469,7 @@ struct GeneralListShape {
   __device__ static __forceinline__ const PlaneCountParams& common(const Args& g) { return g.g.c; }
   __device__ static __forceinline__ uint32_t lmax(const Args& g) { return g.g.lmax; }
   __device__ static __forceinline__ uint32_t offset_of(const Args&, const uint32_t*, uint32_t) { return 0u; }
+  template <bool COLD = false>
   __device__ static __forceinline__ uint32_t test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const Args& g) { return general_test<TOL>(ta, tb, ha, hb, g.g); }
   __device__ static __forceinline__ void classify(const Args&, const uint32_t*, uint64_t, bool, uint32_t& mask, Lens&) { mask = 0; }
 };
@@ -458,7 +480,8 @@ namespace {
 struct WaveState {
   uint32_t* ring;        // LDS, kRing slots: window positions as offsets from the span's first byte, in text order
                          // (capture: the window's bytes 0..3 in ring[kRing + slot], 4..7 in ring[2 kRing + slot])
-  uint32_t* stash;       // LDS, capture: two slots of kStashWords
+  uint32_t* stash;       // LDS, capture: two slots of kStashSlotWords, one ring, aligned to its size
+  uint32_t stash_at;     // ... its LDS address
   uint32_t head, tail;   // wave-uniform, free-running
   uint32_t acc;          // lane p: matches of pattern p so far
   uint32_t flags;        // kPcConflict | kPcVoid (wave-uniform)
@@ -474,22 +497,41 @@ struct WaveState {
 };
 constexpr uint32_t kNoEnd = 0xFFFFFFFFu;
 
+// the LDS word at a 32-bit LDS address
+__device__ __forceinline__ uint32_t lds_word(uint32_t at) {
+  return *(const __attribute__((address_space(3))) uint32_t*)static_cast<uintptr_t>(at);
+}
+
 // the candidates of one block, in text order, to the ring (LIST: to the wave's region in device memory; w.tail counts them)
-// (CAPTURE: block_rel = the block's first byte as an offset from the span's, slot = the block's stash slot)
+// lane_rel = 16 * lane, block_rel = the block's first byte as an offset from the span's.  (CAPTURE: slot = the block's stash
+// slot; the streaming loop passes it as a constant: slot 0's windows end inside the ring, their three words are one address
+// and its immediate offsets)
 template <bool LIST, bool CAPTURE>
-__device__ __forceinline__ void push_block(WaveState& w, uint32_t hm, uint32_t rel_lane, uint32_t block_rel = 0, uint32_t slot = 0) {
+__device__ __forceinline__ void push_block(WaveState& w, uint32_t hm, uint32_t lane_rel, uint32_t block_rel, uint32_t slot = 0) {
   const uint64_t any = __ballot(hm != 0);
   if (any == 0) return;  // wave-uniform
-  auto put = [&](uint32_t idx, uint32_t rel) {
+  // o: the candidate's offset inside the block
+  auto put = [&](uint32_t idx, uint32_t o) {
+    const uint32_t rel = block_rel + o;
     if (LIST) {
       if (idx < w.list_cap) w.list[idx] = w.list_base + rel;
     } else {
       w.ring[idx & (kRing - 1)] = rel;
       if (CAPTURE) {
-        // the window's 8 bytes: three aligned words of the stash, shifted (bytes 2048..2055 = the next block's first 8)
-        const uint32_t o = rel - block_rel;
-        const uint32_t* sw = w.stash + slot * kStashWords + (o >> 2);
-        const uint32_t s0 = sw[0], s1 = sw[1], s2 = sw[2];
+        // the window's 8 bytes: three aligned words of the stash, shifted.  Behind slot 0 lies slot 1, behind slot 1 (the ring's
+        // end) slot 0: whoever stashes or stands in for the block that FOLLOWS has written there before this push.
+        // (slot 1: the stash is aligned to its 4 KiB and o + 8 <= 2 KiB + 4, so "+ 2 KiB, wrapped" is bit 11 flipped)
+        const uint32_t at = w.stash_at + (o & ~3u);
+        uint32_t s0, s1, s2;
+        if (slot == 0) {
+          s0 = lds_word(at);
+          s1 = lds_word(at + 4);
+          s2 = lds_word(at + 8);
+        } else {
+          s0 = lds_word(at + static_cast<uint32_t>(kBlock));
+          s1 = lds_word((at + 4) ^ static_cast<uint32_t>(kBlock));
+          s2 = lds_word((at + 8) ^ static_cast<uint32_t>(kBlock));
+        }
         w.ring[kRing + (idx & (kRing - 1))] = __builtin_amdgcn_alignbyte(s1, s0, o & 3u);
         w.ring[2 * kRing + (idx & (kRing - 1))] = __builtin_amdgcn_alignbyte(s2, s1, o & 3u);
       }
@@ -504,7 +546,7 @@ __device__ __forceinline__ void push_block(WaveState& w, uint32_t hm, uint32_t r
     if (hm != 0) {
       const uint32_t bit = static_cast<uint32_t>(__builtin_ctz(hm));
       const uint32_t at = hm_a != 0 ? lanes_below(any_a) : static_cast<uint32_t>(__popcll(any_a)) + lanes_below(any & ~any_a);
-      put(w.tail + at, rel_lane + (bit >> 1) + ((bit & 1u) ? kPieceB : 0u));
+      put(w.tail + at, lane_rel | (bit >> 1) | ((bit & 1u) ? kPieceB : 0u));
     }
     w.tail += static_cast<uint32_t>(__popcll(any));
     return;
@@ -517,9 +559,9 @@ __device__ __forceinline__ void push_block(WaveState& w, uint32_t hm, uint32_t r
   if (LIST || tot <= kRing) {   // (ring: more -- the caller's occupancy test voids the run; nothing is written)
     const uint32_t before = inc - c;
     uint32_t idx = w.tail + (before & 0xFFFFu);
-    for (uint32_t m = hm_a; m; m &= m - 1, idx++) put(idx, rel_lane + (static_cast<uint32_t>(__builtin_ctz(m)) >> 1));
+    for (uint32_t m = hm_a; m; m &= m - 1, idx++) put(idx, lane_rel | (static_cast<uint32_t>(__builtin_ctz(m)) >> 1));
     idx = w.tail + tot_a + (before >> 16);
-    for (uint32_t m = hm_b; m; m &= m - 1, idx++) put(idx, rel_lane + kPieceB + (static_cast<uint32_t>(__builtin_ctz(m)) >> 1));
+    for (uint32_t m = hm_b; m; m &= m - 1, idx++) put(idx, lane_rel | kPieceB | (static_cast<uint32_t>(__builtin_ctz(m)) >> 1));
   }
   w.tail += tot;
 }
@@ -654,7 +696,7 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
   __shared__ __attribute__((aligned(16))) uint32_t table[kExactTabWords];
   extern __shared__ __attribute__((aligned(16))) uint32_t blob[];
   __shared__ uint32_t rings[4][kRing * (S::kCapture ? 3 : 1)];
-  __shared__ __attribute__((aligned(16))) uint32_t stashes[4][S::kCapture ? 2 * kStashWords : 4];
+  __shared__ __attribute__((aligned(S::kCapture ? kStashBytes : 16))) uint32_t stashes[4][S::kCapture ? 2 * kStashSlotWords : 4];
   __shared__ uint32_t ends[4][4 * kExactMaxPatterns];
   __shared__ unsigned long long wave_bounds[4][kExactMaxPatterns][2];
   __shared__ uint32_t wave_counts[4][kExactMaxPatterns];
@@ -680,6 +722,7 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
   WaveState w;
   w.ring = rings[wid];
   w.stash = stashes[wid];
+  w.stash_at = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint32_t*)stashes[wid]));
   w.ends = ends[wid];
   w.head = w.tail = 0;
   w.acc = 0;
@@ -712,18 +755,22 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
   Raw ra, rb;
   uint2 behind{0, 0};
   uint32_t c = c0;
-  // capture: block ci's bytes to its stash slot (text order: piece A of lane L at 16 L, piece B at 1024 + 16 L) ...
-  auto stash_put = [&](uint32_t ci, const Raw& r) __attribute__((always_inline)) {
+  // capture: a block's bytes to stash slot `slot` = (the block's index - c0) & 1 (text order: piece A of lane L at 16 L, piece B
+  // at 1024 + 16 L).  The parity counts from the SPAN's first block: inside the loop the slots are constants, and the lane's one
+  // stash address serves all four stores through their immediate offsets.  A block's slot is written again two blocks later,
+  // behind the block's own push (read the loop: stash_put of c + 1, push of c, stash_put of c + 2, push of c + 1).
+  auto stash_put = [&](uint32_t slot, const Raw& r) __attribute__((always_inline)) {
     if constexpr (S::kCapture) {
-      uint32_t* sl = w.stash + (ci & 1u) * kStashWords;
+      uint32_t* sl = w.stash + slot * kStashSlotWords;
       *reinterpret_cast<uint4*>(sl + lane * 4) = r.a;
       *reinterpret_cast<uint4*>(sl + kPieceB / 4 + lane * 4) = r.b;
     }
   };
-  // ... and behind them the first 8 bytes of the block that follows (lane 0's x, y)
-  auto spill_put = [&](uint32_t ci, uint32_t x, uint32_t y) __attribute__((always_inline)) {
+  // Where the block that follows is NOT stashed -- behind the span's last fast block, behind a guarded block --, its first 8
+  // bytes (x, y) go to the head of the slot it would have had, once, before the push that may read them.
+  auto follower_put = [&](uint32_t slot, uint32_t x, uint32_t y) __attribute__((always_inline)) {
     if constexpr (S::kCapture) {
-      if (lane == 0) *reinterpret_cast<uint2*>(w.stash + (ci & 1u) * kStashWords + kBlock / 4) = make_uint2(x, y);
+      if (lane == 0) *reinterpret_cast<uint2*>(w.stash + slot * kStashSlotWords) = make_uint2(x, y);
     }
   };
   if (c < fast_end) {
@@ -753,56 +800,54 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
   __syncthreads();
   if (c < fast_end) {
     uint32_t xa = codes16(ra.a, k), xb = codes16(ra.b, k);   // block c
-    stash_put(c, ra);
+    stash_put(0, ra);
     if (S::kCapture) __builtin_amdgcn_sched_barrier(0);   // (the stash is written before the buffer is loaded again)
     load_block(blk(c + 2), lane_rel, ra);
     const uint32_t behind_codes = (codes4(behind.x, k) >> k.shift) | (codes4(behind.y, k) << (8 - k.shift));
     // two blocks per iteration: x = the codes of block c, rb = block c + 1, ra = block c + 2 (in flight)
+    // (ahead: block c + 3, a scalar pointer that advances with the loop; block c + 4 is its immediate offset)
+    const uint8_t* ahead = a.text + (static_cast<uint64_t>(c) + 3) * kBlock;
     while (c + 1 < fast_end) {
       const uint32_t ya = codes16(rb.a, k), yb = codes16(rb.b, k);   // block c + 1
       // (the codes must exist BEFORE the buffer is loaded again: when the compiler sinks their computation towards its
       // use, the reload lands in other registers and is copied back at the loop's end -- behind a wait for it)
       asm volatile("" ::"v"(ya), "v"(yb));
-      stash_put(c + 1, rb);
-      spill_put(c, rb.a.x, rb.a.y);
+      stash_put(1, rb);
       if (S::kCapture) __builtin_amdgcn_sched_barrier(0);
-      if (c + 3 <= last_own) load_block(blk(c + 3), lane_rel, rb);
+      if (c + 3 <= last_own) load_block(ahead, lane_rel, rb);
       {
         // (behind lane 63's piece A: lane 0's piece B; behind its piece B: lane 0's piece A of the next block)
         const uint32_t ha = wave_from_lane_above(xa, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(xb))));
         const uint32_t hb = wave_from_lane_above(xb, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(ya))));
         const uint32_t hm = S::test(xa, xb, ha, hb, g);
-        push_block<S::kList, S::kCapture>(w, hm, (c - c0) * static_cast<uint32_t>(kBlock) + lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), c & 1u);
+        push_block<S::kList, S::kCapture>(w, hm, lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), 0u);
       }
       __builtin_amdgcn_sched_barrier(0);
       xa = codes16(ra.a, k);   // block c + 2 (stale bytes when c + 2 == fast_end: not used then)
       xb = codes16(ra.b, k);
       asm volatile("" ::"v"(xa), "v"(xb));
-      if (c + 2 < fast_end) {
-        stash_put(c + 2, ra);
-        spill_put(c + 1, ra.a.x, ra.a.y);
-      } else {
-        spill_put(c + 1, behind.x, behind.y);
-      }
+      if (c + 2 < fast_end) stash_put(0, ra);
+      else follower_put(0, behind.x, behind.y);   // (the span's last fast block: `behind` stands in for block c + 2)
       if (S::kCapture) __builtin_amdgcn_sched_barrier(0);
-      if (c + 4 <= last_own) load_block(blk(c + 4), lane_rel, ra);
+      if (c + 4 <= last_own) load_block(ahead, lane_rel, ra, static_cast<uint32_t>(kBlock));
       {
         const uint32_t next0 = c + 2 == fast_end ? behind_codes : static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(xa)));
         const uint32_t ha = wave_from_lane_above(ya, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(yb))));
         const uint32_t hb = wave_from_lane_above(yb, next0);
         const uint32_t hm = S::test(ya, yb, ha, hb, g);
-        push_block<S::kList, S::kCapture>(w, hm, (c + 1 - c0) * static_cast<uint32_t>(kBlock) + lane_rel, (c + 1 - c0) * static_cast<uint32_t>(kBlock), (c + 1) & 1u);
+        push_block<S::kList, S::kCapture>(w, hm, lane_rel, (c + 1 - c0) * static_cast<uint32_t>(kBlock), 1u);
       }
       __builtin_amdgcn_sched_barrier(0);
       c += 2;
+      ahead += 2 * kBlock;
       if (!S::kList && w.tail - w.head >= a.batch_at) blocks_done<S>(w, tab, g, span_base, first_batch);
     }
     if (c + 1 == fast_end) {   // an odd block left: x holds its codes; behind it the span ends
       const uint32_t ha = wave_from_lane_above(xa, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(xb))));
       const uint32_t hb = wave_from_lane_above(xb, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(behind_codes))));
       const uint32_t hm = S::test(xa, xb, ha, hb, g);
-      spill_put(c, behind.x, behind.y);
-      push_block<S::kList, S::kCapture>(w, hm, (c - c0) * static_cast<uint32_t>(kBlock) + lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), c & 1u);
+      follower_put(1, behind.x, behind.y);   // (c - c0 is even here: the block lies in slot 0)
+      push_block<S::kList, S::kCapture>(w, hm, lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), 0u);
       c++;
     }
     if (!S::kList) blocks_done<S>(w, tab, g, span_base, first_batch);
@@ -823,17 +868,17 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
     const uint32_t h0 = guarded_dword(a.text, a.n, bt + 16), h1 = guarded_dword(a.text, a.n, bt + 20);
     const uint32_t ha = (codes4(g0, k) >> k.shift) | (codes4(g1, k) << (8 - k.shift));
     const uint32_t hb = (codes4(h0, k) >> k.shift) | (codes4(h1, k) << (8 - k.shift));
-    const uint32_t hm = S::test(codes16(va, k), codes16(vb, k), ha, hb, g);
+    const uint32_t hm = S::template test<true>(codes16(va, k), codes16(vb, k), ha, hb, g);
     if (!S::kList && w.tail - w.head > kRing - 64u) blocks_done<S>(w, tab, g, span_base, first_batch);   // (room for this block)
     if constexpr (S::kCapture) {
       Raw gr;
       gr.a = va;
       gr.b = vb;
-      stash_put(c, gr);
+      stash_put((c - c0) & 1u, gr);
       const uint64_t nb = (static_cast<uint64_t>(c) + 1) * kBlock;
-      spill_put(c, guarded_dword(a.text, a.n, nb), guarded_dword(a.text, a.n, nb + 4));
+      follower_put((c - c0 + 1) & 1u, guarded_dword(a.text, a.n, nb), guarded_dword(a.text, a.n, nb + 4));
     }
-    push_block<S::kList, S::kCapture>(w, hm, (c - c0) * static_cast<uint32_t>(kBlock) + lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), c & 1u);
+    push_block<S::kList, S::kCapture>(w, hm, lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), (c - c0) & 1u);
   }
   if constexpr (S::kList) {
     if (lane == 0) g.hit_counts[wave] = w.tail;   // (also beyond the region's capacity: the classification reports the overflow)
@@ -872,11 +917,21 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
   if (lane == 0) wave_flags[wid] = w.flags;
   __syncthreads();
   if (wid != 0 || lane >= kExactMaxPatterns) return;
+  // The rows' three pointers are read from the argument block HERE, a second time: taken from the copy the kernel's entry loaded
+  // they would sit in six scalar registers across the streaming loop, which needs those for the sixteen pick indices of the
+  // test (102 in all).  (The empty statement hides from the compiler that this is the block it has read before.)
+  const __attribute__((address_space(4))) char* again = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(again));
+  again += reinterpret_cast<const char*>(&a) - reinterpret_cast<const char*>(&g);
+  const auto* rows = reinterpret_cast<const __attribute__((address_space(4))) PlaneCountParams*>(again);
+  uint32_t* const wg_rows = rows->wg_rows;
+  unsigned long long* const wg_bounds = rows->wg_bounds;
+  unsigned long long* const wg_clock = rows->wg_clock;
   // (all four waves are through their spans: the workgroup's exit.  One plain 16-byte store, like the row's)
-  if (lane == 0) *reinterpret_cast<ulonglong2*>(a.wg_clock + static_cast<uint64_t>(blockIdx.x) * 2) = ulonglong2{clock_in, __builtin_amdgcn_s_memrealtime()};
+  if (lane == 0) *reinterpret_cast<ulonglong2*>(wg_clock + static_cast<uint64_t>(blockIdx.x) * 2) = ulonglong2{clock_in, __builtin_amdgcn_s_memrealtime()};
   uint32_t v = wave_counts[0][lane] + wave_counts[1][lane] + wave_counts[2][lane] + wave_counts[3][lane];
   if (lane == kExactMaxPatterns - 1) v = wave_flags[0] | wave_flags[1] | wave_flags[2] | wave_flags[3];   // (slot 31: the flags)
-  a.wg_rows[static_cast<uint64_t>(blockIdx.x) * kExactMaxPatterns + lane] = v;
+  wg_rows[static_cast<uint64_t>(blockIdx.x) * kExactMaxPatterns + lane] = v;
   if (lane < static_cast<int>(a.n_patterns) && v != 0) {   // (the waves of a workgroup hold consecutive spans)
     unsigned long long first = kPcNone, last = kPcNone;
 #pragma unroll
@@ -885,7 +940,7 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
 #pragma unroll
     for (int q = 0; q < 4; q++)
       if (wave_bounds[q][lane][1] != kPcNone) last = wave_bounds[q][lane][1];
-    *reinterpret_cast<ulonglong2*>(a.wg_bounds + (static_cast<uint64_t>(blockIdx.x) * kExactMaxPatterns + lane) * 2) = ulonglong2{first, last};
+    *reinterpret_cast<ulonglong2*>(wg_bounds + (static_cast<uint64_t>(blockIdx.x) * kExactMaxPatterns + lane) * 2) = ulonglong2{first, last};
   }
 }
 
