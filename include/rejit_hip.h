@@ -765,6 +765,56 @@ int64_t rj_scan_records_csv(rj_scan* scan, const void* d_text, uint64_t n, int d
                             uint64_t row_cap, uint64_t* d_field_begin, uint64_t* d_field_end,
                             uint32_t* d_field_flags /* field_cap each */, uint64_t field_cap, rj_csv_stats* stats /* host, required */,
                             void* hip_stream);
+/* Several columns of records written AS QUOTED CSV LINES (rejit_amd/csrc/record_csv_format.hip): the
+ * inverse of rj_scan_records_csv -- Python's csv.writer, Arrow's write_csv -- as a new device text and its record table,
+ * without a download.  cols: n_cols (1..16) columns, a HOST array of rj_zip_column exactly as rj_scan_records_zip takes it
+ * (rows as rj_scan_records_pack's: any order, repeats allowed, a non-NULL list with count 0 is no rows; columns may share a
+ * text and a table; every column has the same row count k); width and reserved must be 0.  With P the bytes of column c's
+ * row j, d = delimiter and q = quote (0..255 each, neither \n nor \r, different from each other):
+ *     special(P)  P holds d, q, \r or \n
+ *     need(c, j)  bit c of always_mask is set, or special(P), or n_cols == 1 and P is empty (csv.writer's lone empty field: "")
+ *     F(c, j)     VALUE column (bit c of raw_mask clear): need ? q + P with every q doubled + q : P
+ *                 RAW column (bit c of raw_mask set):     need ? q + P + q : P -- nothing is doubled: the caller states that P
+ *                 is the interior of a field as rj_scan_records_csv delimits it, its "" still in place; for a field without
+ *                 an RJ_CSV_MALFORMED flag this equals the value rule applied to the field's unescaped value
+ *     T(j)        F(0, j) d F(1, j) d ... F(C-1, j)
+ * and the layout is rj_scan_records_pack's with len(j) = |T(j)|:
+ *     ob(0) = lead, ob(j + 1) = ob(j) + len(j) + gap, total = ob(k)       (k == 0: total = lead)
+ *     d_out[ob(j), ob(j) + len(j)) = T(j); every other byte of d_out[0, total) = fill
+ *     d_out_begin[j] = ob(j), d_out_end[j] = ob(j) + len(j)               (k uint64 each; either may be NULL)
+ * With no always and no raw bits line j is what csv.writer(delimiter=d, quotechar=q, lineterminator="\r\n") writes for the
+ * row, without its terminator; with all always bits the same under quoting=csv.QUOTE_ALL.  A NUL is an ordinary byte.  A
+ * column may be in both masks.  With n_cols = 1 and no piece that needs quotes the output is rj_scan_records_pack's.
+ * flags must be 0.  fill: 0..255; gap may be 0.  d_out: 16-byte aligned, out_cap bytes.  Returns total WHATEVER out_cap is and
+ * never writes at or beyond out_cap; d_out == NULL with out_cap == 0 is the size query (the tables are still written when
+ * given).  With total <= out_cap the result is complete: every byte of [0, total) and every table row is written exactly once,
+ * nothing has to be cleared first, nothing behind total or behind row k is touched.  stats (host, may be NULL): n_rows = k,
+ * n_fields = k n_cols, n_quoted = the fields with need, n_doubled = the quote bytes doubled, total.  Every piece's bytes are
+ * read once to classify them and once to copy them (a value piece of 8 KiB or more with quote bytes inside once more, to count
+ * them in front of every 4-KiB chunk of the output).  The scan lends scratch only (8 + 16 n_cols bytes per row and 16 bytes per
+ * 4 KiB of min(out_cap, lead + k R) with the R of the refusals below -- pass the size query's total as out_cap, not "a large
+ * number", where rows repeat long records --, shared with rj_scan_records_zip): spans, stats and the state of its last rj_scan_records stay as they were.
+ * One synchronise per call.
+ * Refusals (RJ_BAD_ARGUMENT; a refused call writes no output byte and no table row): a bad index or a bad row in any column
+ * -- the message names the first one, "row <j> column <c> ": the smallest j, and at that j the smallest c --; n_cols outside
+ * 1..16; columns whose k differ (both are named); width != 0; reserved != 0; any flag bit; fill, delimiter or quote outside
+ * 0..255; a delimiter or quote that is \n or \r; delimiter == quote; a mask bit at or above n_cols; a null text with n > 0, a
+ * null table with k > 0, a null d_out with out_cap > 0; a table or index list that is not 8-byte aligned; a d_out that is not
+ * 16-byte aligned; R >= 2^42 with R = sum over the columns of (2 n + 2) + (n_cols - 1) + gap, or lead + k R >= 2^62.
+ * k >= 2^31: RJ_TOO_LARGE.  An output that overlaps an input is undefined, as elsewhere in the family.
+ * What stays out: no quoting at all (quote == -1) and escape characters -- rj_scan_records_zip joins without quoting;
+ * QUOTE_NONNUMERIC as a mode (set always_mask for the columns that hold strings); multi-byte delimiters; a line terminator
+ * other than what fill and gap give; per-row nulls; header lines. */
+typedef struct rj_csv_format_stats {
+  uint64_t n_rows, n_fields;
+  uint64_t n_quoted;    /* fields written inside quotes                        */
+  uint64_t n_doubled;   /* quote bytes doubled inside them (value columns)     */
+  uint64_t total;
+} rj_csv_format_stats;
+int64_t rj_scan_records_format_csv(rj_scan* scan, const rj_zip_column* cols, int n_cols, int delimiter, int quote,
+                                   uint32_t always_mask, uint32_t raw_mask, unsigned flags, int fill, uint64_t lead, uint64_t gap,
+                                   void* d_out, uint64_t out_cap, uint64_t* d_out_begin, uint64_t* d_out_end,
+                                   rj_csv_format_stats* stats /* host, may be NULL */, void* hip_stream);
 
 /* ---- several patterns over the same device-resident text (regexdna: nine MatchAllCount calls on
  * one text, sample/regexdna.cc:56-70).  When every pattern has a nibble-form window set (DESIGN.md

@@ -8,8 +8,8 @@ from typing import List, Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
-SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "record_time_format.hip", "record_translate.hip", "record_csv.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
-HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_time_format.h", "record_translate.h", "record_csv.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
+SOURCES = ["kernels.hip", "scan_windows.hip", "dense_walk.hip", "select_kernels.hip", "plane_scan.hip", "plane_count.hip", "run_scan.hip", "emit_scan.hip", "dense_streams.hip", "dense_streams_select.hip", "verify_lds.hip", "carry_kernels.hip", "engine.hip", "multi_pattern.hip", "host_api.hip", "record_join.hip", "record_pack.hip", "record_replace.hip", "record_split.hip", "record_group.hip", "record_sort.hip", "record_lookup.hip", "record_parse.hip", "record_time.hip", "record_format.hip", "record_zip.hip", "record_time_format.hip", "record_translate.hip", "record_csv.hip", "record_csv_format.hip", "linear.hip", "exact_replay.hip", "multi_device.hip", "parser.cc", "lowering.cc", "rejit_api.cc"]
+HEADERS = ["kernels.h", "device_program.h", "lowering.h", "carry_scan.h", "behind_walk.h", "exact_replay.h", "engine_internal.h", "table_layout.h", "lds_walk.h", "trace_stamp.h", "dense_swar.h", "dense_streams.h", "tile_lookback.h", "exact_count.h", "plane_args.h", "short_walk.h", "run_scan.h", "kernel_util.h", "wave_ops.h", "plane_codes.h", "stream_load.h", "record_join.h", "record_pack.h", "record_rows.h", "record_replace.h", "record_split.h", "record_group.h", "record_group_build.h", "record_sort.h", "record_lookup.h", "record_parse.h", "record_time.h", "pow5_table.h", "record_format.h", "pow10_table.h", "record_zip.h", "record_time_format.h", "record_translate.h", "record_csv.h", "record_csv_format.h", "record_frame.h", "dense_streams.hip"]  # (dense_streams_select.hip includes dense_streams.hip)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"]  # of every compile (tools/device_code_diff.py uses them too)
 LIB = os.path.join(PKG, "librejit_hip.so")
 
@@ -191,6 +191,10 @@ class _CsvStats(ctypes.Structure):
                                                "first_bad")]
 
 
+class _CsvFormatStats(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("n_rows", "n_fields", "n_quoted", "n_doubled", "total")]
+
+
 class CsvResult:
     """What Scan.csv_records returns: the tables of rj_scan_records_csv as tensors on the text's device -- row_first (int64,
     n_rows + 1), row_begin / row_end (int64, n_rows; None with rows=False), field_begin / field_end (int64, n_fields),
@@ -255,7 +259,7 @@ C_ABI_SYMBOLS = ["rj_compile", "rj_program_free", "rj_program_info", "rj_last_er
                  "rj_multi_bounds_device", "rj_carry_decide", "rj_multi_start", "rj_multi_finish", "rj_multi_order_after",
                  "rj_multi_device_counts", "rj_multi_device_counts_via", "rj_multi_set_tail_stream", "rj_multi_set_timing", "rj_scan_set_timing", "rj_set_default_timing",
                  "rj_scan_gather_spans", "rj_scan_gather_spans_via", "rj_scan_gathered_spans", "rj_multi_set_counts_only", "rj_scan_stats_sized", "rj_scan_copy_gathered_spans", "rj_scan_count", "rj_host_stats", "rj_replace_all_begin", "rj_replace_all_fetch",
-                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip", "rj_scan_records_format_time", "rj_scan_records_translate", "rj_scan_records_csv"]
+                 "rj_scan_records", "rj_scan_records_select", "rj_scan_records_pack", "rj_scan_records_replace", "rj_scan_records_split", "rj_scan_records_group", "rj_scan_records_sort", "rj_scan_records_lookup", "rj_scan_records_parse", "rj_scan_records_parse_time", "rj_scan_records_format", "rj_scan_records_zip", "rj_scan_records_format_time", "rj_scan_records_translate", "rj_scan_records_csv", "rj_scan_records_format_csv"]
 
 
 def load_library():
@@ -384,6 +388,9 @@ def load_library():
     L.rj_scan_records_translate.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, cp, cp, ctypes.c_int, u64, u64, vp, u64, vp, vp, ctypes.POINTER(_TranslateStats), vp]
     L.rj_scan_records_csv.restype = i64
     L.rj_scan_records_csv.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, vp, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(_CsvStats), vp]
+    L.rj_scan_records_format_csv.restype = i64
+    L.rj_scan_records_format_csv.argtypes = [vp, ctypes.POINTER(ZipColumn), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint,
+                                             ctypes.c_int, u64, u64, vp, u64, vp, vp, ctypes.POINTER(_CsvFormatStats), vp]
     _lib = L
     return L
 
@@ -1309,6 +1316,78 @@ class Scan:
         if total > out.numel():
             raise RejitError(-4, "zip_records: the text has %d bytes, `out` %d" % (total, out.numel()))
         return out[:total], out_begin, out_end
+
+    def format_csv_records(self, columns, delimiter: bytes = b",", quote: bytes = b'"', always=(), raw=(), fill: int = 10, lead: int = 0, gap: int = 1,
+                           out=None, stream=None, stats: bool = False, flags: int = 0):
+        """rj_scan_records_format_csv: the inverse of csv_records -- the rows of several columns written as quoted CSV lines on
+        the device.  `columns` is zip_records' list (1 to 16) of (text, rec_begin, rec_end) or (text, rec_begin, rec_end,
+        indices).  Line j is the columns' rows j joined with the byte `delimiter`; a field that holds the delimiter, the
+        quote, \\r or \\n -- or whose column is listed in `always`, or the lone empty field of a one-column line -- stands
+        between two `quote` bytes with every quote byte inside doubled, exactly as Python's csv.writer quotes it.  A column
+        listed in `raw` holds the interiors of fields as csv_records delimits them (their "" still in place): it is quoted
+        by the same rule, but nothing is doubled.  Returns (out_text, out_begin, out_end) as zip_records does -- `gap` bytes of
+        `fill` (default: a newline) behind every line, `lead` in front; without `out` one size query and an exact allocation,
+        with `out` (contiguous uint8, 16-byte aligned) one call and RejitError when it is too small -- and with stats=True a
+        fourth value, rj_csv_format_stats as a dict.  The scan's spans, stats and select_records stay as they were."""
+        import torch
+
+        columns = [tuple(c) for c in columns]
+        if not columns:
+            raise RejitError(-4, "format_csv_records: no columns (a call takes 1 to 16)")
+        byte = lambda x, name: int(x) if isinstance(x, int) else (bytes(x)[0] if len(bytes(x)) == 1 else _raise(ValueError("format_csv_records: %s is not one byte" % name)))
+        delimiter, quote = byte(delimiter, "delimiter"), byte(quote, "quote")
+        mask = lambda listed, name: sum({1 << (int(c) if 0 <= int(c) < 32 else _raise(ValueError("format_csv_records: %s names column %d" % (name, c)))) for c in listed})
+        always_mask, raw_mask = mask(always, "always"), mask(raw, "raw")
+        device = columns[0][0].device
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else 0
+        cols = (ZipColumn * len(columns))()
+        keep = []
+        k = None
+        for c, column in enumerate(columns):
+            if len(column) not in (3, 4):
+                raise ValueError("format_csv_records: a column is (text, rec_begin, rec_end) or (text, rec_begin, rec_end, indices)")
+            t, rb, re_ = column[:3]
+            indices = column[3] if len(column) == 4 else None
+            assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda and t.device == device
+            n_records = int(rb.numel())
+            for x in (rb, re_):
+                assert x.dtype == torch.int64 and x.is_contiguous() and x.device == device and x.numel() == n_records
+            rows = n_records
+            if indices is not None:
+                assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == device
+                rows = int(indices.numel())
+                if rows == 0:
+                    indices = torch.zeros(1, dtype=torch.int64, device=device)   # (a non-null pointer: NULL means every record)
+                    keep.append(indices)
+            k = rows if k is None else k
+            cols[c] = ZipColumn(ptr(t), int(t.numel()), ptr(rb), ptr(re_), n_records, indices.data_ptr() if indices is not None else 0,
+                                rows if indices is not None else 0, 0, 0)
+        st = torch.cuda.current_stream(device).cuda_stream if stream is None else stream
+        out_begin = torch.empty(k, dtype=torch.int64, device=device)
+        out_end = torch.empty(k, dtype=torch.int64, device=device)
+        cs = _CsvFormatStats()
+
+        def call(buf, cap):
+            return int(_check(self._lib.rj_scan_records_format_csv(self._h, cols, len(columns), delimiter, quote, always_mask, raw_mask, int(flags), int(fill),
+                                                                   int(lead), int(gap), ctypes.c_void_p(ptr(buf)) if cap else None, cap,
+                                                                   ctypes.c_void_p(ptr(out_begin)), ctypes.c_void_p(ptr(out_end)),
+                                                                   ctypes.byref(cs) if stats else None, ctypes.c_void_p(st))))
+
+        def result(text):
+            if not stats:
+                return text, out_begin, out_end
+            return text, out_begin, out_end, {f: int(getattr(cs, f)) for f, _ in _CsvFormatStats._fields_}
+        if out is None:
+            total = call(None, 0)
+            out = torch.empty(total, dtype=torch.uint8, device=device)
+            if total:
+                call(out, total)
+            return result(out)
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == device
+        total = call(out, int(out.numel()))
+        if total > out.numel():
+            raise RejitError(-4, "format_csv_records: the text has %d bytes, `out` %d" % (total, out.numel()))
+        return result(out[:total])
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""

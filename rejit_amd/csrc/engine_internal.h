@@ -177,7 +177,8 @@ struct rj_scan {
   // the 16 bytes per row between its plan and its emit
   rejit_amd::DeviceBuffer rec_format_stage;
   // rj_scan_records_zip (record_zip.hip) shares the summary, the look-back words and rec_pack_begin; rec_zip_stage: the rows'
-  // lengths (8 bytes per row), then the 16 bytes per piece between its resolve and its emit
+  // lengths (8 bytes per row), then the 16 bytes per piece between its resolve and its emit.  rj_scan_records_format_csv
+  // (record_csv_format.hip) borrows all of these, rec_zip_stage with the same layout.
   rejit_amd::DeviceBuffer rec_zip_stage;
   // rj_scan_records_translate (record_translate.hip) shares the summary and the look-back words; rec_translate_stage: the rows'
   // places in its virtual stream (8 bytes per row), then the kept bytes before each unit of slabs (8 bytes per unit)

@@ -238,6 +238,26 @@ def csv_bad_rows(row_first, field_flags):
     return upto[row_first[1:]] > upto[row_first[:-1]]
 
 
+def csv_cut(scan, text, csv_result, cols, delimiter: bytes = b",", quote: bytes = b'"', rows=None, fill: int = 10, lead: int = 0, gap: int = 1):
+    """(out_text, out_begin, out_end): the columns `cols` (0-based; negative: counted from the row's end, as csv_column) of the
+    rows of Scan.csv_records' result -- all of them, or those the int64 tensor `rows` names -- written as CSV lines again by
+    Scan.format_csv_records, in that order, as a packed device text with its record table.  The fields go in as RAW columns
+    straight from the original text -- their interiors as csv_records delimits them, `""` still in place: no pack, no
+    unescape --, so a field comes out quoted exactly when its value needs it.  A ragged row's absent column is written as an
+    empty field.  Rows with a CSV_MALFORMED field are the caller's to leave out (csv_bad_rows).  `scan` lends scratch only."""
+    import torch
+
+    columns = []
+    for c in cols:
+        index, present = csv_column(csv_result.row_first, int(c))
+        if rows is not None:
+            index, present = index[rows], present[rows]
+        begin = csv_result.field_begin[index].contiguous()
+        end = torch.where(present, csv_result.field_end[index], begin).contiguous()
+        columns.append((text, begin, end))
+    return scan.format_csv_records(columns, delimiter=delimiter, quote=quote, raw=range(len(columns)), fill=fill, lead=lead, gap=gap)
+
+
 def csv_values(scan, text, field_begin, field_end, field_flags, indices=None, quote: bytes = b'"', fill: int = 10):
     """(out_text, out_begin, out_end): the VALUES of the fields of Scan.csv_records -- all of them, or those `indices` names
     (csv_column) -- as a packed device text with its record table, a doubled quote read as one.  When no chosen field is

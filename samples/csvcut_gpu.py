@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""csvcut_gpu.py FILE (-c COLS | -g N -a M) [-d DELIM] -- columns of a CSV file with quoted fields, with everything between
+"""csvcut_gpu.py FILE (-c COLS | -C COLS | -g N -a M) [-d DELIM] -- columns of a CSV file with quoted fields, with everything between
 the upload and the answer on the GPU:
 
     the file is uploaded once; rj_scan_records_csv (Scan.csv_records) reads its rows and fields -- a delimiter or a line break
@@ -8,6 +8,9 @@ the upload and the answer on the GPU:
 
   -c COLS   print the columns COLS (1-based, comma separated, in that order) of every row, tab-separated, one row per line;
             a row without such a column prints an empty value (`csvcut -c`, values unquoted)
+  -C COLS   print the same columns as CSV again, with the input's delimiter: a field that holds the delimiter, a quote or a line
+            break stands in quotes, as Python's csv.writer writes it (records.csv_cut: rj_scan_records_format_csv over the
+            fields' interiors in the uploaded text -- no pack, no unescape; `csvcut -c`)
   -g N -a M   print every distinct value of column N, in order of first appearance, a tab, and the int64 sum of column M over
             its rows (rj_scan_records_group, rj_scan_records_parse, records.group_sums, rj_scan_records_format); a value of M
             that is not an integer [+-]?[0-9]+ (spaces and tabs around it dropped) adds 0
@@ -30,13 +33,14 @@ def option(argv, name):
 
 def main(argv):
     cols, argv = option(argv, "-c")
+    csv_cols, argv = option(argv, "-C")
     group, argv = option(argv, "-g")
     agg, argv = option(argv, "-a")
     delim, argv = option(argv, "-d")
     delim = b"," if delim is None else os.fsencode(delim)
     numbers = lambda s: s is not None and all(x.isdigit() and int(x) >= 1 for x in s.split(","))
-    if len(argv) != 1 or len(delim) != 1 or (cols is None) == (group is None) or (group is None) != (agg is None) or (
-            cols is not None and not numbers(cols)) or (group is not None and not (group.isdigit() and agg.isdigit() and int(group) >= 1 and int(agg) >= 1)):
+    if len(argv) != 1 or len(delim) != 1 or (cols is not None) + (csv_cols is not None) + (group is not None) != 1 or (group is None) != (agg is None) or (
+            cols is not None and not numbers(cols)) or (csv_cols is not None and not numbers(csv_cols)) or (group is not None and not (group.isdigit() and agg.isdigit() and int(group) >= 1 and int(agg) >= 1)):
         sys.stderr.write(__doc__)
         return 2
     import numpy as np
@@ -72,7 +76,9 @@ def main(argv):
         index, present = records.csv_column(table.row_first, c - 1)
         vt, vb, ve = records.csv_values(scan, text, table.field_begin, table.field_end, table.field_flags, indices=index[good].contiguous())
         return vt, vb, torch.where(present[good], ve, vb).contiguous()
-    if cols is not None:
+    if csv_cols is not None:
+        printed, _, _ = records.csv_cut(scan, text, table, [int(c) - 1 for c in csv_cols.split(",")], delimiter=delim, rows=good)
+    elif cols is not None:
         printed, _, _ = scan.zip_records([column(int(c)) for c in cols.split(",")], sep=b"\t")
     else:
         kt, kb, ke = column(int(group))
