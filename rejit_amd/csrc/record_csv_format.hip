@@ -9,13 +9,14 @@
 //   csvf::kWaveBytes or more is taken by the lane's whole wave instead, 64 lanes x 16 bytes a step (the two tiers of the group
 //   call's hash pass).  It stages 16 bytes per piece (source, length, quote count, need), the row's length, and leaves the
 //   first bad (row, column) in the summary: one atomic max per wave.  It writes no table row: the check stands in front of the plan.
-// Plan: record_frame.h's plan_units over the staged lengths; ob / oe and the total.  Returns at once behind a bad row.
+// Plan: record_frame.h's plan_staged_lengths (plan_units over the staged lengths); ob / oe and the total.  Returns at once behind a bad row.
 // Checkpoint: returns at once unless the classify met an expanding piece of csvf::kCheckpointBytes or more.  A wave per row:
 //   lane c places column c's field from the staged pieces (a wave prefix sum of the field lengths), and every such piece is
 //   walked ONCE by the wave, 64 lanes x 16 bytes a step, counting its quote bytes: where a step's output holds a chunk's first
 //   byte, it leaves (the step, the quote bytes in front of it) as that chunk's checkpoint -- 16 bytes per 4-KiB chunk of
 //   min(out_cap, lead + k R), the most the emit can write.  A chunk's first byte lies in one piece at the most: every entry has one writer, and nothing is cleared first.
-// Emit: output-major and persistent in chunks of 4 KiB through an image in LDS, the zip's emit with three tiers (csvf::tier_of):
+// Emit: record_frame.h's emit_chunks -- output-major and persistent in chunks of 4 KiB through an image in LDS --, the zip's policy
+//   with three tiers (csvf::tier_of) and a phase between the rows and the store:
 //     bytes   every row of the chunk once, by its own lane: delimiters, the quotes around a field, the short pieces (doubled
 //             inline), the partial groups at the two ends of a piece that streams (csvf::row_edges)
 //     expand  a long value piece with quote bytes inside: the row's lane only lists it; then one wave per listed piece walks
@@ -39,7 +40,7 @@ namespace rejit_amd {
 
 namespace {
 
-static_assert(csvf::kEmitChunk == kThreads * pack::kGroupBytes, "one pass of the workgroup fills or stores the chunk's image");
+static_assert(csvf::kEmitChunk == kImageChunk, "the header's chunk is the frame's");
 static_assert(csvf::kWaveStep == kWave * rows::kGroupBytes, "a wave's step is 64 lanes x 16 bytes");
 
 // the call's counts in the summary (words the frame's calls leave to their callers)
@@ -118,9 +119,7 @@ __global__ __launch_bounds__(kThreads) void record_csv_format_plan_kernel(const 
                                                                           unsigned long long* granules, unsigned long long* ticket, uint64_t n_units,
                                                                           uint64_t* __restrict__ out_begin, uint64_t* __restrict__ out_end,
                                                                           unsigned long long* summary) {
-  if (refused(summary)) return;
-  const auto row = [=](uint64_t j) { return PlannedRow{0, row_len[j]}; };
-  plan_units(row, k, lead, gap, granules, ticket, n_units, out_begin, out_end, summary);
+  plan_staged_lengths(row_len, k, lead, gap, granules, ticket, n_units, out_begin, out_end, summary);
 }
 
 // record_csv_format.h's Source over the kernel's arguments and the stage
@@ -175,102 +174,69 @@ __global__ __launch_bounds__(kThreads) void record_csv_format_checkpoint_kernel(
   }
 }
 
+// The emit: record_frame.h's emit_chunks with the zip's stream tier and, between the rows and the store, the expand walk over
+// the pieces the rows' lanes listed (the chunk's list, LDS).
+struct ExpandList {
+  uint64_t row[csvf::kMaxExpand], at[csvf::kMaxExpand];
+  uint32_t col[csvf::kMaxExpand];
+};
+struct CsvFormatEmit : StreamingImagePolicy {
+  uint32_t& s_expands;   // the pieces listed (they fit: kMaxExpand's assert)
+  ExpandList& list;
+  const csvf::Columns& cols;
+  const DeviceSource& src;
+  const uint64_t* __restrict__ ob;
+  const csvf::Checkpoint* __restrict__ checkpoints;
+  uint32_t n_cols, delimiter, quote, raw_mask;
+  int lane;   // (made once in front of the chunks: made in `between`, the walk's loop compiles to other, slower code)
+  __device__ __forceinline__ void reset() const { s_streams = 0, s_expands = 0; }
+  // bytes: the row's edges; the pieces that expand are listed
+  __device__ __forceinline__ bool row(uint64_t j, uint64_t c0, uint64_t c1, const ImagePut& put) const {
+    const uint64_t at = ob[j];
+    if (at >= c1) return false;
+    return csvf::row_edges(src, n_cols, delimiter, quote, raw_mask, j, at, c0, c1, put, [&](uint64_t row, uint32_t col, uint64_t data0) {
+      const uint32_t i = atomicAdd(&s_expands, 1u);   // (LDS)
+      if (i < csvf::kMaxExpand) list.row[i] = row, list.at[i] = data0, list.col[i] = col;
+    });
+  }
+  // expand: a wave per listed piece
+  __device__ __forceinline__ void between(uint64_t c, uint64_t c0, uint64_t c1, const ImagePut& put) const {
+    const uint32_t n_expands = s_expands < csvf::kMaxExpand ? s_expands : csvf::kMaxExpand;   // workgroup-uniform
+    if (!n_expands) return;
+    for (uint32_t i = threadIdx.x >> 6; i < n_expands; i += kWaves) {
+      const uint32_t col = list.col[i];
+      const uint64_t data0 = list.at[i];
+      const csvf::Piece pc = src.piece(list.row[i], col);
+      const DeviceText text{cols.col[col].text, cols.col[col].n};
+      const csvf::Checkpoint from = csvf::resumes(pc, csvf::is_raw(raw_mask, col), data0, c0) ? checkpoints[c] : csvf::Checkpoint{0, 0};
+      uint64_t before = from.before;   // the quote bytes of the piece in front of the step
+      for (uint64_t s = from.s; s < pc.len; s += csvf::kWaveStep) {
+        const uint64_t step_out = data0 + s + before;
+        if (step_out >= c1) break;
+        uint32_t w[4], valid, qbits, below;
+        const uint32_t in_step = walk_step(text, pc, s, lane, quote, w, &valid, &qbits, &below);
+        const uint64_t step_bytes = pc.len - s < csvf::kWaveStep ? pc.len - s : csvf::kWaveStep;
+        if (valid && step_out + step_bytes + in_step > c0)
+          csvf::expand_group(w, valid, qbits, quote, step_out + static_cast<uint64_t>(lane) * rows::kGroupBytes + below, c0, c1, put);
+        before += in_step;
+      }
+    }
+    __syncthreads();
+  }
+  __device__ __forceinline__ bool group16(uint64_t j, uint64_t at, uint64_t p, uint32_t w[4]) const {
+    return csvf::group_streamed(src, n_cols, raw_mask, j, at, p, w);
+  }
+};
 __global__ __launch_bounds__(kThreads) void record_csv_format_emit_kernel(const csvf::Columns cols, uint32_t n_cols, uint32_t delimiter, uint32_t quote,
                                                                           uint32_t raw_mask, const csvf::Staged* __restrict__ stage, uint64_t k,
                                                                           const uint64_t* __restrict__ ob, const csvf::Checkpoint* __restrict__ checkpoints,
                                                                           uint32_t fill, uint8_t* __restrict__ out, uint64_t out_cap,
                                                                           const unsigned long long* summary) {
-  __shared__ uint4 s_image[kThreads];
-  __shared__ uint64_t s_rows[2];
   __shared__ uint32_t s_streams, s_expands;
-  __shared__ uint64_t s_expand_row[csvf::kMaxExpand], s_expand_at[csvf::kMaxExpand];
-  __shared__ uint32_t s_expand_col[csvf::kMaxExpand];
-  if (refused(summary)) return;
-  const uint64_t total = summary[kSumTotal];
-  const uint64_t limit = total < out_cap ? total : out_cap;
-  const uint64_t n_chunks = (limit + csvf::kEmitChunk - 1) / csvf::kEmitChunk;
-  const uint32_t tid = threadIdx.x;
-  const int lane = lane_id();
-  const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
+  __shared__ ExpandList s_list;
   const DeviceSource src{cols, stage, n_cols};
-  uint8_t* image = reinterpret_cast<uint8_t*>(s_image);
-  const uint32_t fw = pack::fill_word(fill);
-  for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const uint64_t c0 = c * csvf::kEmitChunk;
-    const uint64_t c1 = c0 + csvf::kEmitChunk < limit ? c0 + csvf::kEmitChunk : limit;
-    const auto put = [=](uint64_t in_image, uint32_t byte) {
-      if (in_image < csvf::kEmitChunk) image[in_image] = static_cast<uint8_t>(byte);   // (always: every writer clips to the chunk)
-    };
-    // ---- the rows that touch the chunk (two searches side by side), and the image all fill
-    if (tid == 0) s_rows[0] = pack::chunk_first_row(table, k, c0), s_streams = 0, s_expands = 0;
-    if (tid == kWave) s_rows[1] = pack::chunk_end_row(table, k, 0, c1);
-    s_image[tid] = make_uint4(fw, fw, fw, fw);
-    __syncthreads();
-    const uint64_t j0 = s_rows[0], j1 = s_rows[1] > j0 ? s_rows[1] : j0;   // (j1 <= k)
-    // ---- bytes: every row once; the pieces that expand are listed
-    bool any_streamed = false;
-    for (uint64_t j = j0 + tid; j < j1; j += kThreads) {
-      const uint64_t at = ob[j];
-      if (at >= c1) continue;
-      any_streamed |= csvf::row_edges(src, n_cols, delimiter, quote, raw_mask, j, at, c0, c1, put, [&](uint64_t row, uint32_t col, uint64_t data0) {
-        const uint32_t i = atomicAdd(&s_expands, 1u);   // (LDS)
-        if (i < csvf::kMaxExpand) s_expand_row[i] = row, s_expand_at[i] = data0, s_expand_col[i] = col;
-      });
-    }
-    if (any_streamed) s_streams = 1;   // (every writer writes 1)
-    __syncthreads();
-    // ---- expand: a wave per listed piece
-    const uint32_t n_expands = s_expands < csvf::kMaxExpand ? s_expands : csvf::kMaxExpand;   // workgroup-uniform
-    if (n_expands) {
-      for (uint32_t i = tid >> 6; i < n_expands; i += kWaves) {
-        const uint32_t col = s_expand_col[i];
-        const uint64_t data0 = s_expand_at[i];
-        const csvf::Piece pc = src.piece(s_expand_row[i], col);
-        const DeviceText text{cols.col[col].text, cols.col[col].n};
-        const csvf::Checkpoint from = csvf::resumes(pc, csvf::is_raw(raw_mask, col), data0, c0) ? checkpoints[c] : csvf::Checkpoint{0, 0};
-        uint64_t before = from.before;   // the quote bytes of the piece in front of the step
-        for (uint64_t s = from.s; s < pc.len; s += csvf::kWaveStep) {
-          const uint64_t step_out = data0 + s + before;
-          if (step_out >= c1) break;
-          uint32_t w[4], valid, qbits, below;
-          const uint32_t in_step = walk_step(text, pc, s, lane, quote, w, &valid, &qbits, &below);
-          const uint64_t step_bytes = pc.len - s < csvf::kWaveStep ? pc.len - s : csvf::kWaveStep;
-          if (valid && step_out + step_bytes + in_step > c0)
-            csvf::expand_group(w, valid, qbits, quote, step_out + static_cast<uint64_t>(lane) * rows::kGroupBytes + below, c0, c1, put);
-          before += in_step;
-        }
-      }
-      __syncthreads();
-    }
-    // ---- 16 aligned output bytes per lane: streamed where one streaming piece covers them, else the image's
-    const uint64_t p = c0 + static_cast<uint64_t>(tid) * pack::kGroupBytes;
-    if (p < c1) {
-      uint32_t w[4];
-      bool streamed = false;
-      if (s_streams) {
-        const uint64_t u = pack::upper_bound(table, j0, j1, p);   // the last row that begins at or before p has p's bytes
-        if (u > j0) streamed = csvf::group_streamed(src, n_cols, raw_mask, u - 1, ob[u - 1], p, w);
-      }
-      if (!streamed) {
-        const uint4 v = s_image[tid];
-        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-      }
-      const uint32_t bytes = pack::group_store_bytes(p, limit);
-      if (bytes == pack::kGroupBytes) {
-        *reinterpret_cast<uint4*>(out + p) = make_uint4(w[0], w[1], w[2], w[3]);
-      } else {
-        for (uint32_t b = 0; b < bytes; b++) out[p + b] = static_cast<uint8_t>(w[b >> 2] >> (8 * (b & 3)));
-      }
-    }
-    __syncthreads();   // (the next chunk rewrites s_rows, the flags, the list and the image)
-  }
-}
-
-// the chunks of an output of at most `bytes` bytes (no sum that could wrap)
-inline uint64_t chunks_of(uint64_t bytes) { return bytes / csvf::kEmitChunk + (bytes % csvf::kEmitChunk ? 1 : 0); }
-inline unsigned emit_grid(uint64_t most_bytes) {
-  const uint64_t chunks = chunks_of(most_bytes);
-  return static_cast<unsigned>(chunks < kCopyGrid ? chunks : kCopyGrid);
+  emit_chunks(CsvFormatEmit{StreamingImagePolicy(s_streams), s_expands, s_list, cols, src, ob, checkpoints, n_cols, delimiter, quote, raw_mask, lane_id()}, k, ob, fill, out,
+              out_cap, summary);
 }
 
 }  // namespace
@@ -312,7 +278,7 @@ int64_t rj_scan_records_format_csv(rj_scan* s, const rj_zip_column* columns, int
   if ((rc = pack_begin_table(s, d_out_begin, copies, k, &ob)) != RJ_OK) return rc;
   if (k) {   // the rows' lengths, then (a call that copies) the pieces and a checkpoint per chunk of min(out_cap, lead + k R): the zip's scratch
     const uint64_t len_bytes = rows::align16(k * sizeof(uint64_t)), stage_bytes = copies ? k * C * sizeof(csvf::Staged) : 0;
-    RJ_HIP(s->rec_zip_stage.reserve(len_bytes + stage_bytes + (copies ? chunks_of(most_bytes) * sizeof(csvf::Checkpoint) : 0)));
+    RJ_HIP(s->rec_zip_stage.reserve(len_bytes + stage_bytes + (copies ? chunks_of(most_bytes, kImageChunk) * sizeof(csvf::Checkpoint) : 0)));
     row_len = s->rec_zip_stage.as<uint64_t>();
     if (copies) {
       stage = reinterpret_cast<csvf::Staged*>(s->rec_zip_stage.as<uint8_t>() + len_bytes);
@@ -332,7 +298,7 @@ int64_t rj_scan_records_format_csv(rj_scan* s, const rj_zip_column* columns, int
                        static_cast<const csvf::Staged*>(stage), k, static_cast<const uint64_t*>(ob), out_cap, checkpoints, summary);
   }
   if (copies)
-    hipLaunchKernelGGL(record_csv_format_emit_kernel, dim3(emit_grid(most_bytes)), block, 0, st, cols, C, static_cast<uint32_t>(delimiter),
+    hipLaunchKernelGGL(record_csv_format_emit_kernel, dim3(image_grid(most_bytes)), block, 0, st, cols, C, static_cast<uint32_t>(delimiter),
                        static_cast<uint32_t>(quote), raw_mask, static_cast<const csvf::Staged*>(stage), k, static_cast<const uint64_t*>(ob),
                        static_cast<const csvf::Checkpoint*>(checkpoints), static_cast<uint32_t>(fill), static_cast<uint8_t*>(d_out), out_cap, summary);
   if ((rc = records_finish(s, kCall, st)) != RJ_OK) return rc;

@@ -9,7 +9,7 @@
 // shortest() below, the Schubfach algorithm (Giulietti, "The Schubfach way to render doubles", 2020) in integers only -- three
 // 64 x 128 bit products with pow10_table.h's g(k), rounded to odd, and a few comparisons; no fallback, no floating-point
 // operation.  From a Small the row's text follows byte by byte in closed form (Row, char_at): any byte range of a row is
-// produced without the bytes before it, so the answer does not depend on where the output cuts a row (put_bytes, chunk_part).
+// produced without the bytes before it, so the answer does not depend on where the output cuts a row (put_bytes, pack::chunk_part).
 //
 // repr(float): with the digits d1 d2 ... dn and the value 0.d1d2...dn x 10^decpt, the form is positional for -4 < decpt <= 16
 // (a `.0` behind an integer), else d1[.d2...dn]e+-XX with at least two exponent digits; -0.0 is `-0.0`; the non-finite values
@@ -22,6 +22,7 @@
 
 #include "pow10_table.h"
 #include "record_pack.h"
+#include "record_rows.h"
 
 // (forced inline on the device: a Row handed to a function that is not inlined would live in scratch memory)
 #if defined(__HIPCC__)
@@ -48,7 +49,6 @@ RJ_FORMAT_HD bool sums_fit(uint64_t k, uint64_t lead, uint64_t gap) { return pac
 
 // what rj_scan_records_format refuses before it launches anything, in this order (the first bad index is found by its check kernel)
 enum Refusal : int { kFine = 0, kNullArgument, kTableAlign, kOutAlign, kBadKind, kBadFlags, kBadFill, kBadSums, kTooManyRows };
-constexpr uint64_t kMaxRows = 1ull << 31;   // (record_rows.h's rows_fit: the record calls take fewer rows than this)
 RJ_FORMAT_HD Refusal check_call(const void* value, const void* status, uint64_t n_values, const void* indices, uint64_t n_indices, int kind,
                                      unsigned flags, int fill, uint64_t lead, uint64_t gap, const void* out, uint64_t out_cap, const void* out_begin,
                                      const void* out_end) {
@@ -63,7 +63,7 @@ RJ_FORMAT_HD Refusal check_call(const void* value, const void* status, uint64_t 
   if (!flags_known(flags)) return kBadFlags;
   if (fill < 0 || fill > 255) return kBadFill;
   if (!sums_fit(k, lead, gap)) return kBadSums;
-  if (k >= kMaxRows) return kTooManyRows;
+  if (!rows::rows_fit(k)) return kTooManyRows;
   return kFine;
 }
 
@@ -290,14 +290,8 @@ RJ_FORMAT_HD void put_bytes(const Row& r, uint32_t from, uint32_t count, uint32_
   for (uint32_t i = 0; i < count; i++) put_byte(w, at + i, char_at(r, from + i));
 }
 
-// The emit works chunk by chunk of the output: the part of the row at [ob, ob + len) that lies inside the chunk [c0, c1) is
-// the row's bytes [*lo, *hi); false: none of it does.
-RJ_FORMAT_HD bool chunk_part(uint64_t ob, uint32_t len, uint64_t c0, uint64_t c1, uint32_t* lo, uint32_t* hi) {
-  if (ob >= c1 || ob + len <= c0) return false;
-  *lo = ob < c0 ? static_cast<uint32_t>(c0 - ob) : 0u;
-  *hi = ob + len > c1 ? static_cast<uint32_t>(c1 - ob) : len;
-  return *lo < *hi;
-}
+// (record_pack.h's chunk_part under this header's name: one definition, the name its callers have always used)
+using pack::chunk_part;
 
 }  // namespace numformat
 }  // namespace rejit_amd

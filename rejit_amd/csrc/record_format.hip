@@ -14,7 +14,7 @@
 //   the index, the status and the digit count in it that kernel needs 98 VGPRs, four waves per SIMD, against 60 and eight:
 //   the 32 bytes per row of the stage are the cheaper price.)  The row's length goes into the scan; ob / oe and the total are
 //   written.
-// Emit: output-major as record_frame.h's copy_chunks, in chunks of 4 KiB (one pass of 256 lanes x 16 bytes), the chunk
+// Emit: record_frame.h's emit_chunks -- output-major as copy_chunks, in chunks of 4 KiB (one pass of 256 lanes x 16 bytes), the chunk
 //   built in LDS: its rows from one pair of searches over ob, every row converted once by its own lane -- the digits from the
 //   staged Small (or from the integer itself) by the header's closed form -- into an image of the chunk that was filled with
 //   the fill byte, then one 16-byte store of the image per lane.  No byte stores to memory but the last group's below the total,
@@ -29,15 +29,9 @@ namespace rejit_amd {
 
 namespace {
 
-constexpr uint64_t kEmitChunk = 4096;
-
 __global__ __launch_bounds__(kThreads) void record_format_check_kernel(const uint64_t* __restrict__ indices, uint64_t n_values, uint64_t k, uint64_t n_units,
                                                                        unsigned long long* summary) {
-  for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-    const uint64_t j = unit * kThreads + threadIdx.x;
-    const bool bad = j < k && indices[j] >= n_values;
-    note_bad_row(bad, j, &summary[kSumBadWord]);
-  }
+  check_indices(indices, n_values, k, n_units, summary);
 }
 
 // the row's value as a Small; every index has passed the check
@@ -64,66 +58,28 @@ __global__ __launch_bounds__(kThreads) void record_format_plan_kernel(const uint
   plan_units(row, k, lead, gap, granules, ticket, n_units, out_begin, out_end, summary);
 }
 
-// The emit: a sibling of record_frame.h's copy_chunks -- output-major, persistent, the total read from the summary, the rows of
-// a chunk from the same pair of searches -- whose chunk is built in LDS: rows are 0 to 24 bytes at any offset, so a chunk of 4
-// KiB holds hundreds of them, and a lane that searched for the rows under its 16 bytes would convert a row once per group
-// it touches.  Here every row of the chunk is converted ONCE, by its own lane, into the chunk's image in LDS (filled with the
-// fill byte first), and behind a barrier every lane stores 16 aligned bytes of the image.  The rows of a chunk are not
-// bounded (empty rows with gap 0): the lanes take them 256 at a time.
+// The emit: record_frame.h's emit_chunks; a row's bytes are the digits of the staged Small by the header's closed form.
+struct FormatEmit : ImagePolicy {
+  const ulonglong2* __restrict__ stage;
+  const uint64_t* __restrict__ ob;
+  __device__ __forceinline__ bool row(uint64_t j, uint64_t c0, uint64_t c1, const ImagePut& put) const {
+    const ulonglong2 staged = stage[j];
+    const numformat::Small s{staged.x, staged.y};
+    const uint64_t at = ob[j];
+    uint32_t lo, hi;
+    if (!pack::chunk_part(at, numformat::small_len(s), c0, c1, &lo, &hi)) return false;
+    const numformat::Row row = numformat::unfold(s);
+    // (holds: always, by chunk_part -- but char_at made AHEAD of a test is hoisted and unswitched on the row's class, and the kernel
+    // spills 428 registers)
+    for (uint32_t i = lo; i < hi; i++)
+      if (put.holds(at + i - c0)) put(at + i - c0, numformat::char_at(row, i));
+    return false;
+  }
+};
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void record_format_emit_kernel(
     const ulonglong2* __restrict__ stage, uint64_t k, const uint64_t* __restrict__ ob, uint32_t fill, uint8_t* __restrict__ out, uint64_t out_cap,
     const unsigned long long* summary) {
-  static_assert(kEmitChunk == kThreads * pack::kGroupBytes, "one pass of the workgroup fills or stores the chunk's image");
-  __shared__ uint4 s_image[kThreads];
-  __shared__ uint64_t s_rows[2];
-  if (refused(summary)) return;
-  const uint64_t total = summary[kSumTotal];
-  const uint64_t limit = total < out_cap ? total : out_cap;
-  const uint64_t n_chunks = (limit + kEmitChunk - 1) / kEmitChunk;
-  const uint32_t tid = threadIdx.x;
-  const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
-  uint8_t* image = reinterpret_cast<uint8_t*>(s_image);
-  const uint32_t fw = pack::fill_word(fill);
-  for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const uint64_t c0 = c * kEmitChunk;
-    const uint64_t c1 = c0 + kEmitChunk < limit ? c0 + kEmitChunk : limit;
-    // ---- the rows that touch the chunk (two searches side by side), and the image all fill
-    if (tid == 0) s_rows[0] = pack::chunk_first_row(table, k, c0);
-    if (tid == kWave) s_rows[1] = pack::chunk_end_row(table, k, 0, c1);
-    s_image[tid] = make_uint4(fw, fw, fw, fw);
-    __syncthreads();
-    const uint64_t j0 = s_rows[0], j1 = s_rows[1] > j0 ? s_rows[1] : j0;   // (j1 <= k)
-    // ---- every row once: its bytes inside the chunk
-    for (uint64_t j = j0 + tid; j < j1; j += kThreads) {
-      const ulonglong2 staged = stage[j];
-      const numformat::Small s{staged.x, staged.y};
-      const uint64_t at = ob[j];
-      uint32_t lo, hi;
-      if (!numformat::chunk_part(at, numformat::small_len(s), c0, c1, &lo, &hi)) continue;
-      const numformat::Row row = numformat::unfold(s);
-      for (uint32_t i = lo; i < hi; i++) {
-        const uint64_t in_image = at + i - c0;
-        if (in_image < kEmitChunk) image[in_image] = static_cast<uint8_t>(numformat::char_at(row, i));   // (always: chunk_part)
-      }
-    }
-    __syncthreads();
-    // ---- 16 aligned output bytes per lane
-    const uint64_t p = c0 + static_cast<uint64_t>(tid) * pack::kGroupBytes;
-    if (p < c1) {
-      const uint32_t bytes = pack::group_store_bytes(p, limit);
-      if (bytes == pack::kGroupBytes) {
-        *reinterpret_cast<uint4*>(out + p) = s_image[tid];
-      } else {
-        for (uint32_t b = 0; b < bytes; b++) out[p + b] = image[tid * pack::kGroupBytes + b];
-      }
-    }
-    __syncthreads();   // (the next chunk rewrites s_rows and the image)
-  }
-}
-
-inline unsigned emit_grid(uint64_t out_cap) {
-  const uint64_t cap_chunks = (out_cap + kEmitChunk - 1) / kEmitChunk;
-  return static_cast<unsigned>(cap_chunks < kCopyGrid ? cap_chunks : kCopyGrid);
+  emit_chunks(FormatEmit{{}, stage, ob}, k, ob, fill, out, out_cap, summary);
 }
 
 }  // namespace
@@ -162,12 +118,7 @@ int64_t rj_scan_records_format(rj_scan* s, const uint64_t* d_value, const uint8_
   uint64_t* ob = nullptr;
   ulonglong2* stage = nullptr;
   unsigned long long *scratch = nullptr, *summary = nullptr;   // scratch: the ticket, then the look-back's words
-  if ((rc = pack_begin_table(s, d_out_begin, copies, k, &ob)) != RJ_OK) return rc;
-  if (copies && k) {
-    RJ_HIP(s->rec_format_stage.reserve(k * sizeof(ulonglong2)));
-    stage = s->rec_format_stage.as<ulonglong2>();
-  }
-  if ((rc = records_begin(s, 1 + lookback::granule_words(n_units), st, &scratch, &summary)) != RJ_OK) return rc;
+  if ((rc = value_rows_begin(s, d_out_begin, copies, k, n_units, st, &ob, &stage, &scratch, &summary)) != RJ_OK) return rc;
   const dim3 block(kThreads), units(unit_grid(n_units));
   if (d_indices && k) hipLaunchKernelGGL(record_format_check_kernel, units, block, 0, st, d_indices, n_values, k, n_units, summary);
 #define RJ_FORMAT_PLAN(FLOAT)                                                                                                                \
@@ -177,11 +128,10 @@ int64_t rj_scan_records_format(rj_scan* s, const uint64_t* d_value, const uint8_
   else RJ_FORMAT_PLAN(false);
 #undef RJ_FORMAT_PLAN
   if (copies)
-    hipLaunchKernelGGL(record_format_emit_kernel, dim3(emit_grid(out_cap)), block, 0, st, static_cast<const ulonglong2*>(stage), k,
+    hipLaunchKernelGGL(record_format_emit_kernel, dim3(image_grid(out_cap)), block, 0, st, static_cast<const ulonglong2*>(stage), k,
                        static_cast<const uint64_t*>(ob), static_cast<uint32_t>(fill), static_cast<uint8_t*>(d_out), out_cap, summary);
   if ((rc = records_finish(s, kCall, st)) != RJ_OK) return rc;
-  if (s->rec_host[kSumBadWord] != 0)
-    return rj_fail(RJ_BAD_ARGUMENT, "%s: row %llu names no value (index < n_values)", kCall, static_cast<unsigned long long>(~s->rec_host[kSumBadWord]));
+  if (s->rec_host[kSumBadWord] != 0) return bad_index_failure(s, kCall);
   return static_cast<int64_t>(s->rec_host[kSumTotal]);
 }
 

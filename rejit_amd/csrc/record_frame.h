@@ -1,10 +1,12 @@
 // rejit_amd/csrc/record_frame.h -- what the record units (record_join.hip, record_pack.hip, record_replace.hip,
-// record_split.hip, record_group.hip with record_group_build.h, record_sort.hip, record_lookup.hip, record_parse.hip) share, in ONE place: the
+// record_split.hip, record_group.hip with record_group_build.h, record_sort.hip, record_lookup.hip, record_parse.hip, record_time.hip,
+// record_format.hip, record_time_format.hip, record_zip.hip, record_translate.hip, record_csv.hip, record_csv_format.hip) share, in ONE place: the
 // summary words of their calls and when they refuse one, the 64-bit wave sums, the first bad row and the list of flagged
 // rows as a wave leaves them, the 16-byte read of a device text at any alignment (record_rows.h's Text), the rows of a
 // record table, the unit of a persistent scan in arrival order (ticket, publish, resolve, timed-out), the plan over it, the
-// output-major chunk copy, and the host plumbing around the launches.  Everything lives in an anonymous namespace: every
-// unit gets its own copy.
+// output-major chunk copy (record_pack.hip, record_replace.hip), the output-major chunk EMIT through an image in LDS
+// (record_format.hip, record_time_format.hip, record_zip.hip, record_csv_format.hip), the index check of the value-column
+// calls, and the host plumbing around the launches.  Everything lives in an anonymous namespace: every unit gets its own copy.
 #ifndef REJIT_AMD_RECORD_FRAME_H_
 #define REJIT_AMD_RECORD_FRAME_H_
 
@@ -27,6 +29,8 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr uint64_t kCopyChunk = 16384;    // output bytes per chunk: four passes of 256 lanes x 16 bytes
 constexpr unsigned kCopyGrid = 256 * 8;   // persistent: eight workgroups for each of the 256 CUs
+constexpr uint64_t kImageChunk = kThreads * pack::kGroupBytes;   // output bytes per chunk of an emit: ONE pass of 256 lanes x 16 bytes
+static_assert(kImageChunk == 4096, "one pass of the workgroup fills or stores the chunk's image (record_zip.h's kEmitChunk is this number)");
 
 // the summary every record call writes (device words, copied to the scan's pinned copy).  kSumBadWord: the first bad row of
 // the call in the call's own encoding, 0: none -- the LARGEST word wins (one atomic max), and every encoding makes that the
@@ -234,6 +238,26 @@ __device__ __forceinline__ void plan_units(const RowFn& row, uint64_t k, uint64_
   }
 }
 
+// ... over row lengths a kernel in front of it has staged (the zip, the CSV writer); returns at once behind a bad row
+__device__ __forceinline__ void plan_staged_lengths(const uint64_t* __restrict__ row_len, uint64_t k, uint64_t lead, uint64_t gap,
+                                                    unsigned long long* granules, unsigned long long* ticket, uint64_t n_units,
+                                                    uint64_t* __restrict__ out_begin, uint64_t* __restrict__ out_end, unsigned long long* summary) {
+  if (refused(summary)) return;
+  const auto row = [=](uint64_t j) { return PlannedRow{0, row_len[j]}; };
+  plan_units(row, k, lead, gap, granules, ticket, n_units, out_begin, out_end, summary);
+}
+
+// The check of a call whose rows index a column of n_values values: one lane per row, index < n_values; the first bad row
+// wins (note_bad_row).  It stands in front of the plan, which writes its table rows unit by unit: a refused call writes none.
+__device__ __forceinline__ void check_indices(const uint64_t* __restrict__ indices, uint64_t n_values, uint64_t k, uint64_t n_units,
+                                              unsigned long long* summary) {
+  for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
+    const uint64_t j = unit * kThreads + threadIdx.x;
+    const bool bad = j < k && indices[j] >= n_values;
+    note_bad_row(bad, j, &summary[kSumBadWord]);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- copy
 // The copy of a pack: output-major, so a workgroup's work does not depend on the records' sizes.  The output [0, min(total,
 // out_cap)) is cut into chunks; the grid is persistent and reads the total from the summary (the host has not seen it yet).
@@ -291,6 +315,100 @@ __device__ __forceinline__ void copy_chunks(const Policy& P, const uint8_t* __re
       }
     }
     __syncthreads();   // (the next chunk rewrites s_rows and the stage)
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- emit
+// The emit of a call that MAKES its rows' bytes: copy_chunks' sibling -- output-major, persistent, the total read from the
+// summary, the rows of a chunk from the same pair of searches -- whose chunk of kImageChunk bytes is built in LDS.  Rows can be
+// a few bytes at any offset, so a chunk holds hundreds of them, and a lane that searched for the rows under its 16 bytes
+// would make a row once per group it touches.  Here every row of the chunk is written ONCE, by its own lane, into the
+// chunk's image (preset with the fill byte), and behind a barrier every lane stores 16 aligned bytes of it.  The rows of a
+// chunk are not bounded (empty rows with gap 0): the lanes take them 256 at a time.  No byte stores to memory but the last
+// group's below the limit, no atomics.  The policy P supplies (ImagePolicy has the hooks a unit need not say)
+//   P.row(j, c0, c1, put) -> bool     row j's bytes inside [c0, c1) through put(offset in the image, byte); true: a part of
+//                                     the row is left to group16
+//   P.reset()                         lane 0, before the chunk's first barrier: the flags in the unit's own LDS
+//   P.note_streamed(any)              every lane, before the rows' barrier: one of its rows left a part to group16
+//   P.between(c, c0, c1, put)         workgroup-uniform, behind the rows' barrier: a phase of the whole workgroup that writes
+//                                     more of the image, and ends in a barrier of its own when it ran
+//   P.streams() / P.group16(j, at, p, w)   in a chunk where streams() holds: true when the 16 bytes at p, inside row j at
+//                                     `at`, come from registers (w) instead of the image
+// LDS of a unit's own (a layout, a list, the stream flag) is declared in the unit's kernel and reaches the policy by reference.
+// put(offset in the image, byte): the one writer of the image (forced inline: a call inside the rows' loop would spill the row)
+struct ImagePut {
+  uint8_t* image;
+  __device__ __forceinline__ bool holds(uint64_t in_image) const { return in_image < kImageChunk; }
+  __device__ __forceinline__ void operator()(uint64_t in_image, uint32_t byte) const {
+    if (holds(in_image)) image[in_image] = static_cast<uint8_t>(byte);   // (always: every writer clips to the chunk)
+  }
+};
+struct ImagePolicy {
+  __device__ __forceinline__ void reset() const {}
+  __device__ __forceinline__ void note_streamed(bool) const {}
+  __device__ __forceinline__ void between(uint64_t, uint64_t, uint64_t, const ImagePut&) const {}
+  __device__ __forceinline__ bool streams() const { return false; }
+  __device__ __forceinline__ bool group16(uint64_t, uint64_t, uint64_t, uint32_t[4]) const { return false; }
+};
+// ... of a unit with a stream tier: one LDS word says whether a row of the chunk left a part to group16
+struct StreamingImagePolicy : ImagePolicy {
+  uint32_t& s_streams;
+  __device__ __forceinline__ explicit StreamingImagePolicy(uint32_t& flag) : s_streams(flag) {}
+  __device__ __forceinline__ void reset() const { s_streams = 0; }
+  __device__ __forceinline__ void note_streamed(bool any) const {
+    if (any) s_streams = 1;   // (every writer writes 1)
+  }
+  __device__ __forceinline__ bool streams() const { return s_streams != 0; }
+};
+template <class Policy>
+__device__ __forceinline__ void emit_chunks(const Policy& P, uint64_t k, const uint64_t* __restrict__ ob, uint32_t fill, uint8_t* __restrict__ out,
+                                            uint64_t out_cap, const unsigned long long* summary) {
+  __shared__ uint4 s_image[kThreads];
+  __shared__ uint64_t s_rows[2];
+  if (refused(summary)) return;
+  const uint64_t total = summary[kSumTotal];
+  const uint64_t limit = total < out_cap ? total : out_cap;
+  const uint64_t n_chunks = (limit + kImageChunk - 1) / kImageChunk;   // (limit <= total < pack::kMaxTotal: no wrap)
+  const uint32_t tid = threadIdx.x;
+  const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
+  const ImagePut put{reinterpret_cast<uint8_t*>(s_image)};
+  const uint32_t fw = pack::fill_word(fill);
+  for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const uint64_t c0 = c * kImageChunk;
+    const uint64_t c1 = c0 + kImageChunk < limit ? c0 + kImageChunk : limit;
+    // ---- the rows that touch the chunk (two searches side by side), and the image all fill
+    if (tid == 0) s_rows[0] = pack::chunk_first_row(table, k, c0), P.reset();
+    if (tid == kWave) s_rows[1] = pack::chunk_end_row(table, k, 0, c1);
+    s_image[tid] = make_uint4(fw, fw, fw, fw);
+    __syncthreads();
+    const uint64_t j0 = s_rows[0], j1 = s_rows[1] > j0 ? s_rows[1] : j0;   // (j1 <= k)
+    // ---- every row once: its bytes inside the chunk
+    bool any_left = false;
+    for (uint64_t j = j0 + tid; j < j1; j += kThreads) any_left |= P.row(j, c0, c1, put);
+    P.note_streamed(any_left);
+    __syncthreads();
+    P.between(c, c0, c1, put);
+    // ---- 16 aligned output bytes per lane: from registers where the policy has them, else the image's
+    const uint64_t p = c0 + static_cast<uint64_t>(tid) * pack::kGroupBytes;
+    if (p < c1) {
+      uint32_t w[4];
+      bool streamed = false;
+      if (P.streams()) {
+        const uint64_t u = pack::upper_bound(table, j0, j1, p);   // the last row that begins at or before p has p's bytes
+        if (u > j0) streamed = P.group16(u - 1, ob[u - 1], p, w);
+      }
+      if (!streamed) {
+        const uint4 v = s_image[tid];
+        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+      }
+      const uint32_t bytes = pack::group_store_bytes(p, limit);
+      if (bytes == pack::kGroupBytes) {
+        *reinterpret_cast<uint4*>(out + p) = make_uint4(w[0], w[1], w[2], w[3]);
+      } else {
+        for (uint32_t b = 0; b < bytes; b++) out[p + b] = static_cast<uint8_t>(w[b >> 2] >> (8 * (b & 3)));
+      }
+    }
+    __syncthreads();   // (the next chunk rewrites s_rows, the unit's flags and the image)
   }
 }
 
@@ -357,12 +475,35 @@ inline int pack_begin_table(rj_scan* s, uint64_t* d_out_begin, bool copies, uint
   return RJ_OK;
 }
 
-// persistent grids: workgroups take units / chunks until none is left
-inline unsigned unit_grid(uint64_t n_units) { return static_cast<unsigned>(n_units < 1 ? 1 : n_units < 1024 ? n_units : 1024); }
-inline unsigned copy_grid(uint64_t out_cap) {
-  const uint64_t cap_chunks = (out_cap + kCopyChunk - 1) / kCopyChunk;
-  return static_cast<unsigned>(cap_chunks < kCopyGrid ? cap_chunks : kCopyGrid);
+// What the calls over a column of values (rj_scan_records_format, rj_scan_records_format_time) do before their launches: the
+// begin table, 16 bytes of stage per row for a call that copies, the summary and the scratch -- the ticket, then the
+// look-back's words.
+inline int value_rows_begin(rj_scan* s, uint64_t* d_out_begin, bool copies, uint64_t k, uint64_t n_units, hipStream_t st, uint64_t** ob, ulonglong2** stage,
+                            unsigned long long** scratch, unsigned long long** summary) {
+  const int rc = pack_begin_table(s, d_out_begin, copies, k, ob);
+  if (rc != RJ_OK) return rc;
+  *stage = nullptr;
+  if (copies && k) {
+    RJ_HIP(s->rec_format_stage.reserve(k * sizeof(ulonglong2)));
+    *stage = s->rec_format_stage.as<ulonglong2>();
+  }
+  return records_begin(s, 1 + lookback::granule_words(n_units), st, scratch, summary);
 }
+// ... and behind records_finish, when check_indices left a bad row in the summary
+inline int bad_index_failure(const rj_scan* s, const char* call) {
+  return rj_fail(RJ_BAD_ARGUMENT, "%s: row %llu names no value (index < n_values)", call, static_cast<unsigned long long>(~s->rec_host[kSumBadWord]));
+}
+
+// persistent grids: workgroups take units / chunks until none is left.  The chunks of at most `bytes` output bytes are
+// counted without a sum that could wrap: a caller's out_cap may be any "large enough" number.
+inline unsigned unit_grid(uint64_t n_units) { return static_cast<unsigned>(n_units < 1 ? 1 : n_units < 1024 ? n_units : 1024); }
+inline uint64_t chunks_of(uint64_t bytes, uint64_t chunk) { return bytes / chunk + (bytes % chunk != 0); }
+inline unsigned chunk_grid(uint64_t bytes, uint64_t chunk) {
+  const uint64_t chunks = chunks_of(bytes, chunk);
+  return static_cast<unsigned>(chunks < kCopyGrid ? chunks : kCopyGrid);
+}
+inline unsigned copy_grid(uint64_t out_cap) { return chunk_grid(out_cap, kCopyChunk); }
+inline unsigned image_grid(uint64_t bytes) { return chunk_grid(bytes, kImageChunk); }
 
 }  // namespace
 

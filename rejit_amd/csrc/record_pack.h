@@ -157,6 +157,15 @@ RJ_PACK_HD inline int group16(const View& v, const Rows& r, uint64_t p, uint64_t
   return 2;
 }
 
+// An emit that makes its rows' bytes works chunk by chunk of the output: the part of the row at [ob, ob + len) that lies
+// inside the chunk [c0, c1) is the row's bytes [*lo, *hi); false: none of it does.
+RJ_PACK_HD inline bool chunk_part(uint64_t ob, uint32_t len, uint64_t c0, uint64_t c1, uint32_t* lo, uint32_t* hi) {
+  if (ob >= c1 || ob + len <= c0) return false;
+  *lo = ob < c0 ? static_cast<uint32_t>(c0 - ob) : 0u;
+  *hi = ob + len > c1 ? static_cast<uint32_t>(c1 - ob) : len;
+  return *lo < *hi;
+}
+
 // bytes of the group at p a lane stores: all 16 with one vector store, or the few below the limit one by one
 RJ_PACK_HD inline uint32_t group_store_bytes(uint64_t p, uint64_t limit) { return limit - p >= kGroupBytes ? static_cast<uint32_t>(kGroupBytes) : static_cast<uint32_t>(limit - p); }
 

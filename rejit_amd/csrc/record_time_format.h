@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "record_pack.h"
+#include "record_rows.h"
 #include "record_time.h"
 
 // (forced inline on the device: a Source handed to a function that is not inlined would live in scratch memory)
@@ -66,7 +67,6 @@ RJ_TIMEFORMAT_HD bool sums_fit(uint64_t k, uint64_t lead, uint64_t gap) { return
 // what rj_scan_records_format_time refuses before it launches anything, in this order (the format is compiled between kBadFill and
 // kBadSums; the first bad index is found by the check kernel)
 enum Refusal : int { kFine = 0, kNullArgument, kTableAlign, kOutAlign, kBadUnit, kBadZone, kBadFlags, kBadFill, kBadSums, kTooManyRows };
-constexpr uint64_t kMaxRows = 1ull << 31;   // (record_rows.h's rows_fit: the record calls take fewer rows than this)
 RJ_TIMEFORMAT_HD Refusal check_arguments(const void* value, uint64_t n_values, const void* indices, const void* format, uint64_t format_len, int unit,
                                          int zone_minutes, unsigned flags, int fill, const void* out, uint64_t out_cap, const void* out_begin,
                                          const void* out_end) {
@@ -83,7 +83,7 @@ RJ_TIMEFORMAT_HD Refusal check_arguments(const void* value, uint64_t n_values, c
 }
 RJ_TIMEFORMAT_HD Refusal check_sizes(uint64_t k, uint64_t lead, uint64_t gap) {
   if (!sums_fit(k, lead, gap)) return kBadSums;
-  if (k >= kMaxRows) return kTooManyRows;
+  if (!rows::rows_fit(k)) return kTooManyRows;
   return kFine;
 }
 
@@ -268,14 +268,8 @@ RJ_TIMEFORMAT_HD uint32_t source_byte(const Source& s, uint32_t index) {
 // the row's byte whose layout entry is `entry`: one table read (the caller's) and one extraction
 RJ_TIMEFORMAT_HD uint32_t char_at(const Source& s, uint32_t entry) { return (entry & kSource) ? source_byte(s, entry & (kSourceBytes - 1)) : (entry & 0xFFu); }
 
-// The emit works chunk by chunk of the output: the part of the row at [ob, ob + len) that lies inside the chunk [c0, c1) is
-// the row's bytes [*lo, *hi); false: none of it does.
-RJ_TIMEFORMAT_HD bool chunk_part(uint64_t ob, uint32_t len, uint64_t c0, uint64_t c1, uint32_t* lo, uint32_t* hi) {
-  if (ob >= c1 || ob + len <= c0) return false;
-  *lo = ob < c0 ? static_cast<uint32_t>(c0 - ob) : 0u;
-  *hi = ob + len > c1 ? static_cast<uint32_t>(c1 - ob) : len;
-  return *lo < *hi;
-}
+// (record_pack.h's chunk_part under this header's name: one definition, the name its callers have always used)
+using pack::chunk_part;
 
 }  // namespace timeformat
 }  // namespace rejit_amd

@@ -2,7 +2,7 @@
 // index list names -- written as TEXT under a strftime-style format into a new contiguous device text with its record table,
 // laid out exactly as rj_scan_records_format lays its rows out: the inverse of rj_scan_records_parse_time, without a download.
 // record_time_format.h has the meaning (the split of an instant into civil fields, the layout table the format is compiled
-// into, a row's bytes through it); the frame is record_format.hip's: two memsets (the summary, the look-back's words) and up
+// into, a row's bytes through it); the frame is record_format.hip's (record_frame.h's value_rows_begin, check_indices, plan_units, emit_chunks): two memsets (the summary, the look-back's words) and up
 // to three launches on one stream, one synchronise:
 //
 // Check (with an index list only): one lane per row, index < n_values; the first bad row wins (note_bad_row).  A refused call
@@ -13,7 +13,7 @@
 //   class, and the nanoseconds.  The row's length, L or 0, goes into the scan; ob / oe and the total are written.  The three
 //   classes (OK, null status, out of range) are counted with ballots: one LDS atomic per wave, unit and class that occurred,
 //   one global atomic per workgroup and class, into summary words of this call's own.
-// Emit: record_format.hip's shape, output-major in chunks of 4 KiB (one pass of 256 lanes x 16 bytes), the chunk built in LDS:
+// Emit: record_frame.h's emit_chunks, as record_format.hip's: output-major in chunks of 4 KiB (one pass of 256 lanes x 16 bytes), the chunk built in LDS:
 //   its rows from one pair of searches over ob, every row written once by its own lane through the layout table -- copied to
 //   LDS once per workgroup from a kernel argument, by constant indices -- into an image of the chunk that was filled with the
 //   fill byte, then one 16-byte store of the image per lane.  No byte stores to memory but the last group's below the total,
@@ -28,8 +28,6 @@ namespace rejit_amd {
 
 namespace {
 
-constexpr uint64_t kEmitChunk = 4096;
-
 // the summary words of a call: a count per class (kSumBadWord, kSumTotal and kSumTimedOut keep their meaning)
 enum { kSumOk = kSumKept, kSumNull = kSumMatching, kSumRange = kSumCrossing };
 static_assert(kSumRange < kSumBadWord && kSumRange < kSumTotal && kSumRange < kSumTimedOut, "summary words of its own");
@@ -37,11 +35,7 @@ __device__ __forceinline__ uint32_t class_word(uint32_t cls) { return cls == tim
 
 __global__ __launch_bounds__(kThreads) void record_time_format_check_kernel(const uint64_t* __restrict__ indices, uint64_t n_values, uint64_t k, uint64_t n_units,
                                                                             unsigned long long* summary) {
-  for (uint64_t unit = blockIdx.x; unit < n_units; unit += gridDim.x) {
-    const uint64_t j = unit * kThreads + threadIdx.x;
-    const bool bad = j < k && indices[j] >= n_values;
-    note_bad_row(bad, j, &summary[kSumBadWord]);
-  }
+  check_indices(indices, n_values, k, n_units, summary);
 }
 
 template <int kUnit>
@@ -72,71 +66,34 @@ __global__ __launch_bounds__(kThreads) void record_time_format_plan_kernel(const
     atomicAdd(&summary[class_word(threadIdx.x)], static_cast<unsigned long long>(s_count[threadIdx.x]));
 }
 
-// The emit: record_format.hip's -- output-major, persistent, the total read from the summary, the rows of a chunk from the
-// pair of searches, the chunk's image in LDS -- with the row's bytes from the layout table: byte i of every OK row is entry i,
-// a literal or a byte of the row's Source.  The rows of a chunk are not bounded (empty rows with gap 0): the lanes take them
-// 256 at a time.
+// The emit: record_frame.h's emit_chunks; byte i of every OK row is the layout table's entry i, a literal or a byte of the
+// row's Source.  The table is copied to LDS once per workgroup from a kernel argument, by constant indices.
+struct TimeFormatEmit : ImagePolicy {
+  const ulonglong2* __restrict__ stage;
+  const uint64_t* __restrict__ ob;
+  const uint16_t* entries;   // (LDS)
+  uint32_t L;
+  __device__ __forceinline__ bool row(uint64_t j, uint64_t c0, uint64_t c1, const ImagePut& put) const {
+    const ulonglong2 staged = stage[j];
+    const timeformat::Fields f{staged.x, staged.y};
+    const uint64_t at = ob[j];
+    uint32_t lo, hi;
+    if (!pack::chunk_part(at, timeformat::row_len(f, L), c0, c1, &lo, &hi)) return false;
+    const timeformat::Source src = timeformat::unfold(f);
+    for (uint32_t i = lo; i < hi; i++)
+      if (put.holds(at + i - c0) && i < timeformat::kMaxRowBytes) put(at + i - c0, timeformat::char_at(src, entries[i]));   // (always: chunk_part, hi <= L)
+    return false;
+  }
+};
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void record_time_format_emit_kernel(
     const ulonglong2* __restrict__ stage, uint64_t k, const uint64_t* __restrict__ ob, timeformat::Layout layout, uint32_t fill, uint8_t* __restrict__ out,
     uint64_t out_cap, const unsigned long long* summary) {
-  static_assert(kEmitChunk == kThreads * pack::kGroupBytes, "one pass of the workgroup fills or stores the chunk's image");
-  __shared__ uint4 s_image[kThreads];
-  __shared__ uint64_t s_rows[2];
   __shared__ uint32_t s_layout[timeformat::kLayoutWords];
-  if (refused(summary)) return;
-  if (threadIdx.x == kThreads - 1) {
+  if (threadIdx.x == kThreads - 1) {   // (the first chunk's first barrier publishes it)
 #pragma unroll
     for (uint32_t i = 0; i < timeformat::kLayoutWords; i++) s_layout[i] = layout.words[i];
   }
-  const uint16_t* entries = reinterpret_cast<const uint16_t*>(s_layout);
-  const uint32_t L = layout.len;
-  const uint64_t total = summary[kSumTotal];
-  const uint64_t limit = total < out_cap ? total : out_cap;
-  const uint64_t n_chunks = (limit + kEmitChunk - 1) / kEmitChunk;
-  const uint32_t tid = threadIdx.x;
-  const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
-  uint8_t* image = reinterpret_cast<uint8_t*>(s_image);
-  const uint32_t fw = pack::fill_word(fill);
-  for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const uint64_t c0 = c * kEmitChunk;
-    const uint64_t c1 = c0 + kEmitChunk < limit ? c0 + kEmitChunk : limit;
-    // ---- the rows that touch the chunk (two searches side by side), and the image all fill
-    if (tid == 0) s_rows[0] = pack::chunk_first_row(table, k, c0);
-    if (tid == kWave) s_rows[1] = pack::chunk_end_row(table, k, 0, c1);
-    s_image[tid] = make_uint4(fw, fw, fw, fw);
-    __syncthreads();   // (the first one also publishes s_layout)
-    const uint64_t j0 = s_rows[0], j1 = s_rows[1] > j0 ? s_rows[1] : j0;   // (j1 <= k)
-    // ---- every row once: its bytes inside the chunk
-    for (uint64_t j = j0 + tid; j < j1; j += kThreads) {
-      const ulonglong2 staged = stage[j];
-      const timeformat::Fields f{staged.x, staged.y};
-      const uint64_t at = ob[j];
-      uint32_t lo, hi;
-      if (!timeformat::chunk_part(at, timeformat::row_len(f, L), c0, c1, &lo, &hi)) continue;
-      const timeformat::Source src = timeformat::unfold(f);
-      for (uint32_t i = lo; i < hi; i++) {
-        const uint64_t in_image = at + i - c0;
-        if (in_image < kEmitChunk && i < timeformat::kMaxRowBytes) image[in_image] = static_cast<uint8_t>(timeformat::char_at(src, entries[i]));   // (always: chunk_part)
-      }
-    }
-    __syncthreads();
-    // ---- 16 aligned output bytes per lane
-    const uint64_t p = c0 + static_cast<uint64_t>(tid) * pack::kGroupBytes;
-    if (p < c1) {
-      const uint32_t bytes = pack::group_store_bytes(p, limit);
-      if (bytes == pack::kGroupBytes) {
-        *reinterpret_cast<uint4*>(out + p) = s_image[tid];
-      } else {
-        for (uint32_t b = 0; b < bytes; b++) out[p + b] = image[tid * pack::kGroupBytes + b];
-      }
-    }
-    __syncthreads();   // (the next chunk rewrites s_rows and the image)
-  }
-}
-
-inline unsigned emit_grid(uint64_t out_cap) {
-  const uint64_t cap_chunks = (out_cap + kEmitChunk - 1) / kEmitChunk;
-  return static_cast<unsigned>(cap_chunks < kCopyGrid ? cap_chunks : kCopyGrid);
+  emit_chunks(TimeFormatEmit{{}, stage, ob, reinterpret_cast<const uint16_t*>(s_layout), layout.len}, k, ob, fill, out, out_cap, summary);
 }
 
 }  // namespace
@@ -188,12 +145,7 @@ int64_t rj_scan_records_format_time(rj_scan* s, const uint64_t* d_value, const u
   uint64_t* ob = nullptr;
   ulonglong2* stage = nullptr;
   unsigned long long *scratch = nullptr, *summary = nullptr;   // scratch: the ticket, then the look-back's words
-  if ((rc = pack_begin_table(s, d_out_begin, copies, k, &ob)) != RJ_OK) return rc;
-  if (copies && k) {
-    RJ_HIP(s->rec_format_stage.reserve(k * sizeof(ulonglong2)));
-    stage = s->rec_format_stage.as<ulonglong2>();
-  }
-  if ((rc = records_begin(s, 1 + lookback::granule_words(n_units), st, &scratch, &summary)) != RJ_OK) return rc;
+  if ((rc = value_rows_begin(s, d_out_begin, copies, k, n_units, st, &ob, &stage, &scratch, &summary)) != RJ_OK) return rc;
   const dim3 block(kThreads), units(unit_grid(n_units));
   const int32_t zone_seconds = zone_minutes * 60;
   if (d_indices && k) hipLaunchKernelGGL(record_time_format_check_kernel, units, block, 0, st, d_indices, n_values, k, n_units, summary);
@@ -208,11 +160,10 @@ int64_t rj_scan_records_format_time(rj_scan* s, const uint64_t* d_value, const u
   }
 #undef RJ_TIME_FORMAT_PLAN
   if (copies)
-    hipLaunchKernelGGL(record_time_format_emit_kernel, dim3(emit_grid(out_cap)), block, 0, st, static_cast<const ulonglong2*>(stage), k,
+    hipLaunchKernelGGL(record_time_format_emit_kernel, dim3(image_grid(out_cap)), block, 0, st, static_cast<const ulonglong2*>(stage), k,
                        static_cast<const uint64_t*>(ob), layout, static_cast<uint32_t>(fill), static_cast<uint8_t*>(d_out), out_cap, summary);
   if ((rc = records_finish(s, kCall, st)) != RJ_OK) return rc;
-  if (s->rec_host[kSumBadWord] != 0)
-    return rj_fail(RJ_BAD_ARGUMENT, "%s: row %llu names no value (index < n_values)", kCall, static_cast<unsigned long long>(~s->rec_host[kSumBadWord]));
+  if (s->rec_host[kSumBadWord] != 0) return bad_index_failure(s, kCall);
   if (stats) *stats = rj_format_time_stats{s->rec_host[kSumOk], s->rec_host[kSumNull], s->rec_host[kSumRange]};
   return static_cast<int64_t>(s->rec_host[kSumTotal]);
 }

@@ -10,9 +10,9 @@
 //   every chunk a row touches -- and the row's length, and leaves the first bad (row, column) in the summary: one atomic max
 //   per wave.  It writes no table row: a refused call leaves ob / oe as they were, which a plan that writes its rows unit by
 //   unit cannot promise -- so the check stands in front of the plan, as in record_format.hip.
-// Plan: record_frame.h's plan_units over the staged lengths, one lane per row, a unit = 256 rows, the decoupled look-back;
+// Plan: record_frame.h's plan_staged_lengths -- plan_units over the staged lengths, one lane per row, a unit = 256 rows, the decoupled look-back;
 //   ob / oe and the total.  Returns at once behind a bad row.
-// Emit: output-major and persistent, a sibling of copy_chunks and of the format's emit: chunks of 4 KiB (one pass of 256
+// Emit: record_frame.h's emit_chunks, the frame of the format's emit -- output-major and persistent, a sibling of copy_chunks: chunks of 4 KiB (one pass of 256
 //   lanes x 16 bytes), the total from the summary, a chunk's rows from the pair of searches over ob.  Two tiers inside it, by a
 //   segment's length (zip::kStreamBytes = 32):
 //     bytes   every row of the chunk once, by its own lane: the separators, the short pieces and paddings, and the partial
@@ -33,7 +33,7 @@ namespace rejit_amd {
 
 namespace {
 
-static_assert(zip::kEmitChunk == kThreads * pack::kGroupBytes, "one pass of the workgroup fills or stores the chunk's image");
+static_assert(zip::kEmitChunk == kImageChunk, "the header's chunk is the frame's");
 
 __global__ __launch_bounds__(kThreads) void record_zip_resolve_kernel(const zip::Columns cols, uint32_t n_cols, uint64_t sep_len, uint64_t k, uint64_t n_units,
                                                                       ulonglong2* __restrict__ stage, uint64_t* __restrict__ row_len,
@@ -64,9 +64,7 @@ __global__ __launch_bounds__(kThreads) void record_zip_plan_kernel(const uint64_
                                                                    unsigned long long* granules, unsigned long long* ticket, uint64_t n_units,
                                                                    uint64_t* __restrict__ out_begin, uint64_t* __restrict__ out_end,
                                                                    unsigned long long* summary) {
-  if (refused(summary)) return;
-  const auto row = [=](uint64_t j) { return PlannedRow{0, row_len[j]}; };
-  plan_units(row, k, lead, gap, granules, ticket, n_units, out_begin, out_end, summary);
+  plan_staged_lengths(row_len, k, lead, gap, granules, ticket, n_units, out_begin, out_end, summary);
 }
 
 // record_zip.h's Source over the kernel's arguments and the stage
@@ -85,69 +83,29 @@ struct DeviceSource {
   __device__ __forceinline__ void load16(uint32_t c, uint64_t s, uint32_t w[4]) const { DeviceText{cols.col[c].text, cols.col[c].n}.load16(s, w); }
 };
 
+// The emit: record_frame.h's emit_chunks with a stream tier -- the rows' edges into the image, the long segments from registers
+struct ZipEmit : StreamingImagePolicy {
+  const DeviceSource& src;
+  const uint64_t* __restrict__ ob;
+  uint32_t n_cols;
+  uint64_t sep_len;
+  uint32_t pad;
+  __device__ __forceinline__ bool row(uint64_t j, uint64_t c0, uint64_t c1, const ImagePut& put) const {
+    const uint64_t at = ob[j];
+    if (at >= c1) return false;
+    return zip::row_edges(src, n_cols, sep_len, pad, j, at, c0, c1, put);
+  }
+  __device__ __forceinline__ bool group16(uint64_t j, uint64_t at, uint64_t p, uint32_t w[4]) const {
+    return zip::group_streamed(src, n_cols, sep_len, pad, j, at, p, w);
+  }
+};
 // (73 VGPRs, six waves per SIMD: held to 64 for eight, the compiler spills 10 of them to scratch memory -- not worth two waves)
 __global__ __launch_bounds__(kThreads) void record_zip_emit_kernel(
     const zip::Columns cols, const zip::Sep sep, uint32_t n_cols, uint64_t sep_len, uint32_t pad, const ulonglong2* __restrict__ stage, uint64_t k,
     const uint64_t* __restrict__ ob, uint32_t fill, uint8_t* __restrict__ out, uint64_t out_cap, const unsigned long long* summary) {
-  __shared__ uint4 s_image[kThreads];
-  __shared__ uint64_t s_rows[2];
   __shared__ uint32_t s_streams;
-  if (refused(summary)) return;
-  const uint64_t total = summary[kSumTotal];
-  const uint64_t limit = total < out_cap ? total : out_cap;
-  const uint64_t n_chunks = (limit + zip::kEmitChunk - 1) / zip::kEmitChunk;
-  const uint32_t tid = threadIdx.x;
-  const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
   const DeviceSource src{cols, sep, stage, n_cols};
-  uint8_t* image = reinterpret_cast<uint8_t*>(s_image);
-  const uint32_t fw = pack::fill_word(fill);
-  for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const uint64_t c0 = c * zip::kEmitChunk;
-    const uint64_t c1 = c0 + zip::kEmitChunk < limit ? c0 + zip::kEmitChunk : limit;
-    // ---- the rows that touch the chunk (two searches side by side), and the image all fill
-    if (tid == 0) s_rows[0] = pack::chunk_first_row(table, k, c0), s_streams = 0;
-    if (tid == kWave) s_rows[1] = pack::chunk_end_row(table, k, 0, c1);
-    s_image[tid] = make_uint4(fw, fw, fw, fw);
-    __syncthreads();
-    const uint64_t j0 = s_rows[0], j1 = s_rows[1] > j0 ? s_rows[1] : j0;   // (j1 <= k)
-    // ---- bytes: every row once -- its separators, short segments, and the partial groups of its long ones
-    bool any_streamed = false;
-    for (uint64_t j = j0 + tid; j < j1; j += kThreads) {
-      const uint64_t at = ob[j];
-      if (at >= c1) continue;
-      any_streamed |= zip::row_edges(src, n_cols, sep_len, pad, j, at, c0, c1, [=](uint64_t in_image, uint32_t byte) {
-        if (in_image < zip::kEmitChunk) image[in_image] = static_cast<uint8_t>(byte);   // (always: the edges are clipped to the chunk)
-      });
-    }
-    if (any_streamed) s_streams = 1;   // (every writer writes 1)
-    __syncthreads();
-    // ---- 16 aligned output bytes per lane: streamed where one long segment covers them, else the image's
-    const uint64_t p = c0 + static_cast<uint64_t>(tid) * pack::kGroupBytes;
-    if (p < c1) {
-      uint32_t w[4];
-      bool streamed = false;
-      if (s_streams) {
-        const uint64_t u = pack::upper_bound(table, j0, j1, p);   // the last row that begins at or before p has p's bytes
-        if (u > j0) streamed = zip::group_streamed(src, n_cols, sep_len, pad, u - 1, ob[u - 1], p, w);
-      }
-      if (!streamed) {
-        const uint4 v = s_image[tid];
-        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-      }
-      const uint32_t bytes = pack::group_store_bytes(p, limit);
-      if (bytes == pack::kGroupBytes) {
-        *reinterpret_cast<uint4*>(out + p) = make_uint4(w[0], w[1], w[2], w[3]);
-      } else {
-        for (uint32_t b = 0; b < bytes; b++) out[p + b] = static_cast<uint8_t>(w[b >> 2] >> (8 * (b & 3)));
-      }
-    }
-    __syncthreads();   // (the next chunk rewrites s_rows, s_streams and the image)
-  }
-}
-
-inline unsigned emit_grid(uint64_t out_cap) {
-  const uint64_t cap_chunks = (out_cap + zip::kEmitChunk - 1) / zip::kEmitChunk;
-  return static_cast<unsigned>(cap_chunks < kCopyGrid ? cap_chunks : kCopyGrid);
+  emit_chunks(ZipEmit{StreamingImagePolicy(s_streams), src, ob, n_cols, sep_len, pad}, k, ob, fill, out, out_cap, summary);
 }
 
 }  // namespace
@@ -197,7 +155,7 @@ int64_t rj_scan_records_zip(rj_scan* s, const rj_zip_column* columns, int n_cols
   hipLaunchKernelGGL(record_zip_plan_kernel, units, block, 0, st, static_cast<const uint64_t*>(row_len), k, lead, gap, scratch + 1, scratch, n_units, ob,
                      d_out_end, summary);
   if (copies)
-    hipLaunchKernelGGL(record_zip_emit_kernel, dim3(emit_grid(out_cap)), block, 0, st, cols, sep_bytes, C, sep_len, static_cast<uint32_t>(pad),
+    hipLaunchKernelGGL(record_zip_emit_kernel, dim3(image_grid(out_cap)), block, 0, st, cols, sep_bytes, C, sep_len, static_cast<uint32_t>(pad),
                        static_cast<const ulonglong2*>(stage), k, static_cast<const uint64_t*>(ob), static_cast<uint32_t>(fill), static_cast<uint8_t*>(d_out),
                        out_cap, summary);
   if ((rc = records_finish(s, kCall, st)) != RJ_OK) return rc;

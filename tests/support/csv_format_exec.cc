@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_csv_format.h"
+#include "checked_image.h"
 #include "checked_table.h"
 #include "checked_text.h"
 
@@ -184,16 +185,8 @@ struct Made {
 Made make_chunk(const CheckedSource& src, const pack::View& table, uint64_t j0, uint64_t j1, uint32_t d, uint32_t q, uint32_t raw_mask, uint32_t fill,
                 uint64_t c0, uint64_t c1, uint64_t chunk, Checkpoints* cps, std::vector<uint8_t>* got) {
   Made m;
-  std::vector<uint8_t> image(chunk, static_cast<uint8_t>(fill)), image_once(chunk, 0);
-  const auto put = [&](uint64_t in_image, uint32_t byte) {
-    if (in_image >= chunk || in_image >= c1 - c0 || byte > 255) {
-      m.left_range = true;
-      return;
-    }
-    if (image_once[in_image]) m.twice = true;
-    image_once[in_image] = 1;
-    image[in_image] = static_cast<uint8_t>(byte);
-  };
+  CheckedImage image(chunk, fill, c0, c1);
+  const auto put = [&](uint64_t in_image, uint32_t byte) { image.put(in_image, byte); };
   struct Listed {
     uint64_t j, data0;
     uint32_t c;
@@ -238,28 +231,15 @@ Made make_chunk(const CheckedSource& src, const pack::View& table, uint64_t j0, 
       before += st.in_step;
     }
   }
-  m.used_stream = any_streamed;
-  got->assign(c1 - c0, 0);
-  for (uint64_t p = c0; p < c1; p += pack::kGroupBytes) {
-    uint32_t w[4] = {0, 0, 0, 0};
-    bool streamed = false;
-    if (any_streamed) {
-      const uint64_t u = pack::upper_bound(table, j0, j1, p);
-      if (u > j0) streamed = csvf::group_streamed(src, src.n_cols, raw_mask, u - 1, table.ob_at(u - 1), p, w);
-    }
-    const uint64_t in_group = c1 - p < pack::kGroupBytes ? c1 - p : pack::kGroupBytes;
-    if (streamed) {
-      m.streamed++;
-      for (uint64_t b = 0; b < in_group; b++)
-        if (image_once[p - c0 + b]) m.twice = true;   // a byte under a streamed group was written as a byte too
-    } else {
-      m.from_image++;
-      for (uint32_t b = 0; b < pack::kGroupBytes; b++)
-        if (p - c0 + b < chunk) w[b >> 2] |= static_cast<uint32_t>(image[p - c0 + b]) << (8 * (b & 3));
-    }
-    for (uint64_t b = 0; b < in_group; b++) (*got)[p - c0 + b] = static_cast<uint8_t>(w[b >> 2] >> (8 * (b & 3)));
-  }
-  m.left_range |= src.any_left();
+  image.store(
+      [&](uint64_t p, uint32_t w[4]) {
+        if (!any_streamed) return false;
+        const uint64_t u = pack::upper_bound(table, j0, j1, p);
+        return u > j0 && csvf::group_streamed(src, src.n_cols, raw_mask, u - 1, table.ob_at(u - 1), p, w);
+      },
+      got);
+  m.streamed = image.streamed, m.from_image = image.from_image, m.used_stream = any_streamed;
+  m.twice |= image.twice, m.left_range |= image.left_range || src.any_left();
   return m;
 }
 
@@ -338,31 +318,19 @@ extern "C" long cfe_format(const csvf::Column* cols, int n_cols, int delimiter, 
   summary[0] = total;
   // ---- emit
   const uint64_t limit = total < out_cap ? total : out_cap;
-  const uint64_t n_chunks = (limit + chunk - 1) / chunk;
   const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
   const CheckedSource src(cols, C, &stage, k);
   bool left_range = counts.left_range;
   Checkpoints cps;
   checkpoint_all(src, table, 0, k, q, raw_mask, chunk, limit, &cps);
   summary[12] = cps.steps;
-  std::vector<uint8_t> got;
-  for (uint64_t c = 0; c < n_chunks; c++) {
-    const uint64_t c0 = c * chunk;
-    const uint64_t c1 = c0 + chunk < limit ? c0 + chunk : limit;
-    const uint64_t j0 = pack::chunk_first_row(table, k, c0);
-    const uint64_t e = pack::chunk_end_row(table, k, 0, c1);
-    const uint64_t j1 = e > j0 ? e : j0;
-    if (j1 > k) return -1;
-    const Made m = make_chunk(src, table, j0, j1, d, q, raw_mask, static_cast<uint32_t>(fill), c0, c1, chunk, &cps, &got);
-    summary[4]++;
+  const long chunks = walk_chunks(table, k, total, chunk, out, out_cap, [&](uint64_t c0, uint64_t c1, uint64_t j0, uint64_t j1, std::vector<uint8_t>* got) {
+    const Made m = make_chunk(src, table, j0, j1, d, q, raw_mask, static_cast<uint32_t>(fill), c0, c1, chunk, &cps, got);
     summary[5] += m.streamed, summary[6] += m.from_image, summary[7] += m.expanded, summary[11] += m.rewalked;
     twice |= m.twice, left_range |= m.left_range;
-    for (uint64_t p = c0; p < c1; p += pack::kGroupBytes) {
-      uint32_t w[4] = {0, 0, 0, 0};
-      for (uint64_t b = 0; b < pack::kGroupBytes && p + b < c1; b++) w[b >> 2] |= static_cast<uint32_t>(got[p - c0 + b]) << (8 * (b & 3));
-      if (!store_group(out, 0, p, limit, out_cap, w)) return -1;
-    }
-  }
+  });
+  if (chunks < 0) return -1;
+  summary[4] = static_cast<uint64_t>(chunks);
   return left_range || twice || cps.twice || cps.unwritten || cps.left_range ? -1 : 0;
 }
 

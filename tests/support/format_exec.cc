@@ -16,7 +16,7 @@
 
 #include "../../rejit_amd/csrc/record_format.h"
 #include "../../rejit_amd/csrc/record_parse.h"
-#include "checked_text.h"
+#include "checked_image.h"
 
 using namespace rejit_amd;
 
@@ -134,50 +134,25 @@ extern "C" long fe_format(const uint64_t* value, const uint8_t* status, uint64_t
   const uint64_t total = lead + before;
   summary[0] = total;
   // ---- emit: the chunk's image (the kernel's LDS) filled, every row of the chunk once, the image stored in groups of 16
-  const uint64_t limit = total < out_cap ? total : out_cap;
-  const uint64_t n_chunks = (limit + chunk - 1) / chunk;
   const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
-  std::vector<uint8_t> image(chunk), image_once(chunk), byte_once(limit, 0);
-  for (uint64_t c = 0; c < n_chunks; c++) {
-    const uint64_t c0 = c * chunk;
-    const uint64_t c1 = c0 + chunk < limit ? c0 + chunk : limit;
-    const uint64_t j0 = pack::chunk_first_row(table, k, c0);
-    const uint64_t e = pack::chunk_end_row(table, k, 0, c1);
-    const uint64_t j1 = e > j0 ? e : j0;
-    if (j1 > k) return -1;
-    summary[2]++;
-    for (uint64_t i = 0; i < chunk; i++) image[i] = static_cast<uint8_t>(fill), image_once[i] = 0;
+  const long chunks = walk_chunks(table, k, total, chunk, out, out_cap, [&](uint64_t c0, uint64_t c1, uint64_t j0, uint64_t j1, std::vector<uint8_t>* got) {
+    CheckedImage image(chunk, static_cast<uint32_t>(fill), c0, c1);
     for (uint64_t j = j0; j < j1; j++) {
-      if (j >= stage.size()) return -1;
-      const numformat::Small s = stage[j];
+      const numformat::Small s = stage[j];   // (j < j1 <= k)
       uint32_t lo, hi;
-      if (!numformat::chunk_part(ob[j], numformat::small_len(s), c0, c1, &lo, &hi)) continue;
-      if (hi > numformat::small_len(s)) return -1;
+      if (!pack::chunk_part(ob[j], numformat::small_len(s), c0, c1, &lo, &hi)) continue;
+      if (hi > numformat::small_len(s)) left_range = true;
       summary[6]++;
       // (the bytes through put_bytes in groups, as the piecewise check of fe_row: the kernel's char_at loop is the same function)
       const numformat::Row row = numformat::unfold(s);
-      for (uint32_t i = lo; i < hi; i++) {
-        const uint64_t at = ob[j] + i - c0;
-        if (at >= chunk) return -1;
-        if (image_once[at]) twice = true;
-        image_once[at] = 1;
-        image[at] = static_cast<uint8_t>(numformat::char_at(row, i));
-      }
+      for (uint32_t i = lo; i < hi; i++) image.put(ob[j] + i - c0, numformat::char_at(row, i));
     }
-    for (uint64_t p = c0; p < c1; p += pack::kGroupBytes) {
-      uint32_t w[4] = {0, 0, 0, 0};
-      for (uint32_t b = 0; b < pack::kGroupBytes; b++) w[b >> 2] |= static_cast<uint32_t>(image[p - c0 + b]) << (8 * (b & 3));
-      const uint32_t bytes = pack::group_store_bytes(p, limit);
-      for (uint32_t b = 0; b < bytes; b++) {
-        if (byte_once[p + b]) twice = true;
-        byte_once[p + b] = 1;
-      }
-      summary[4]++;
-      if (!store_group(out, 0, p, limit, out_cap, w)) return -1;
-    }
-  }
-  for (uint64_t p = 0; p < limit; p++)
-    if (!byte_once[p]) return -1;
+    image.store(got);
+    summary[4] += image.from_image;
+    left_range |= image.left_range, twice |= image.twice;
+  });
+  if (chunks < 0) return -1;
+  summary[2] = static_cast<uint64_t>(chunks);
   return left_range || twice ? -1 : 0;
 }
 

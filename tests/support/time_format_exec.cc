@@ -17,6 +17,7 @@
 
 #include "../../rejit_amd/csrc/record_time.h"
 #include "../../rejit_amd/csrc/record_time_format.h"
+#include "checked_image.h"
 
 using namespace rejit_amd;
 
@@ -121,7 +122,7 @@ extern "C" long tf_format(const uint64_t* value, const uint8_t* status, uint64_t
       return -4;
     }
   // ---- plan
-  bool twice = false;
+  bool twice = false, left_range = false;
   std::vector<uint64_t> own_begin(k + 1);
   uint64_t* ob = out_begin ? out_begin : own_begin.data();
   std::vector<timeformat::Fields> stage(k);
@@ -141,40 +142,24 @@ extern "C" long tf_format(const uint64_t* value, const uint8_t* status, uint64_t
   }
   const uint64_t total = at;
   // ---- emit
-  const uint64_t limit = total < out_cap ? total : out_cap;
-  const uint64_t n_chunks = (limit + chunk - 1) / chunk;
   const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
-  std::vector<uint8_t> image(chunk), image_once(chunk), byte_once(limit, 0);
-  for (uint64_t c = 0; c < n_chunks; c++) {
-    const uint64_t c0 = c * chunk;
-    const uint64_t c1 = c0 + chunk < limit ? c0 + chunk : limit;
-    const uint64_t j0 = pack::chunk_first_row(table, k, c0);
-    const uint64_t e = pack::chunk_end_row(table, k, 0, c1);
-    const uint64_t j1 = e > j0 ? e : j0;
-    if (j1 > k) return -1;
-    for (uint64_t i = 0; i < chunk; i++) image[i] = static_cast<uint8_t>(fill), image_once[i] = 0;
+  const long chunks = walk_chunks(table, k, total, chunk, out, out_cap, [&](uint64_t c0, uint64_t c1, uint64_t j0, uint64_t j1, std::vector<uint8_t>* got) {
+    CheckedImage image(chunk, static_cast<uint32_t>(fill), c0, c1);
     for (uint64_t j = j0; j < j1; j++) {
-      const timeformat::Fields f = stage[j];
+      const timeformat::Fields f = stage[j];   // (j < j1 <= k)
       uint32_t lo, hi;
-      if (!timeformat::chunk_part(ob[j], timeformat::row_len(f, L), c0, c1, &lo, &hi)) continue;
-      if (hi > L) return -1;
-      const timeformat::Source src = timeformat::unfold(f);
-      for (uint32_t i = lo; i < hi; i++) {
-        const uint64_t in_image = ob[j] + i - c0;
-        if (in_image >= chunk) return -1;
-        if (image_once[in_image]) twice = true;
-        image_once[in_image] = 1;
-        image[in_image] = static_cast<uint8_t>(timeformat::char_at(src, timeformat::layout_entry(layout, i)));
+      if (!pack::chunk_part(ob[j], timeformat::row_len(f, L), c0, c1, &lo, &hi)) continue;
+      if (hi > L) {
+        left_range = true;
+        continue;
       }
+      const timeformat::Source src = timeformat::unfold(f);
+      for (uint32_t i = lo; i < hi; i++) image.put(ob[j] + i - c0, timeformat::char_at(src, timeformat::layout_entry(layout, i)));
     }
-    for (uint64_t p = c0; p < c1; p++) {
-      if (p >= out_cap || byte_once[p]) return -1;
-      byte_once[p] = 1;
-      out[p] = image[p - c0];
-    }
-  }
-  for (uint64_t p = 0; p < limit; p++)
-    if (!byte_once[p]) return -1;
+    image.store(got);
+    left_range |= image.left_range, twice |= image.twice;
+  });
+  if (chunks < 0 || left_range) return -1;
   // ---- the rows read back (a complete output only)
   if (round_trip && total <= out_cap) {
     timeparse::Program reading{};

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../rejit_amd/csrc/record_zip.h"
+#include "checked_image.h"
 #include "checked_table.h"
 #include "checked_text.h"
 
@@ -101,48 +102,27 @@ struct Made {
   bool twice = false, left_range = false, used_stream = false;
 };
 
-// The output bytes [c0, c1) (c0 a multiple of 16) as the emit makes them from rows [j0, j1): the image, then group by group.
-// got[i] = byte c0 + i.  ob(j) through `table`.
+// The output bytes [c0, c1) (c0 a multiple of 16) as the emit makes them from rows [j0, j1): the image (`room` bytes), then
+// group by group.  got[i] = byte c0 + i.  ob(j) through `table`.
 Made make_chunk(const CheckedSource& src, const pack::View& table, uint64_t j0, uint64_t j1, uint64_t sep_len, uint32_t pad, uint32_t fill, uint64_t c0,
-                uint64_t c1, uint64_t chunk, std::vector<uint8_t>* got) {
-  Made m;
-  std::vector<uint8_t> image(chunk, static_cast<uint8_t>(fill)), image_once(chunk, 0);
+                uint64_t c1, uint64_t room, std::vector<uint8_t>* got) {
+  CheckedImage image(room, fill, c0, c1);
   bool any_streamed = false;
   for (uint64_t j = j0; j < j1; j++) {
     const uint64_t at = table.ob_at(j);
     if (at >= c1) continue;
-    any_streamed |= zip::row_edges(src, src.n_cols, sep_len, pad, j, at, c0, c1, [&](uint64_t in_image, uint32_t byte) {
-      if (in_image >= chunk || in_image >= c1 - c0) {
-        m.left_range = true;
-        return;
-      }
-      if (image_once[in_image]) m.twice = true;
-      image_once[in_image] = 1;
-      image[in_image] = static_cast<uint8_t>(byte);
-    });
+    any_streamed |= zip::row_edges(src, src.n_cols, sep_len, pad, j, at, c0, c1, [&](uint64_t in_image, uint32_t byte) { image.put(in_image, byte); });
   }
-  m.used_stream = any_streamed;
-  got->assign(c1 - c0, 0);
-  for (uint64_t p = c0; p < c1; p += pack::kGroupBytes) {
-    uint32_t w[4] = {0, 0, 0, 0};
-    bool streamed = false;
-    if (any_streamed) {
-      const uint64_t u = pack::upper_bound(table, j0, j1, p);
-      if (u > j0) streamed = zip::group_streamed(src, src.n_cols, sep_len, pad, u - 1, table.ob_at(u - 1), p, w);
-    }
-    const uint64_t in_group = c1 - p < pack::kGroupBytes ? c1 - p : pack::kGroupBytes;
-    if (streamed) {
-      m.streamed++;
-      for (uint64_t b = 0; b < in_group; b++)
-        if (image_once[p - c0 + b]) m.twice = true;   // a byte under a streamed group was written as a byte too
-    } else {
-      m.from_image++;
-      for (uint32_t b = 0; b < pack::kGroupBytes; b++)
-        if (p - c0 + b < chunk) w[b >> 2] |= static_cast<uint32_t>(image[p - c0 + b]) << (8 * (b & 3));
-    }
-    for (uint64_t b = 0; b < in_group; b++) (*got)[p - c0 + b] = static_cast<uint8_t>(w[b >> 2] >> (8 * (b & 3)));
-  }
-  m.left_range |= src.any_left();
+  image.store(
+      [&](uint64_t p, uint32_t w[4]) {
+        if (!any_streamed) return false;
+        const uint64_t u = pack::upper_bound(table, j0, j1, p);
+        return u > j0 && zip::group_streamed(src, src.n_cols, sep_len, pad, u - 1, table.ob_at(u - 1), p, w);
+      },
+      got);
+  Made m;
+  m.streamed = image.streamed, m.from_image = image.from_image, m.used_stream = any_streamed;
+  m.twice = image.twice, m.left_range = image.left_range || src.any_left();
   return m;
 }
 
@@ -216,29 +196,16 @@ extern "C" long ze_zip(const zip::Column* cols, int n_cols, const char* sep, uin
   const uint64_t total = lead + before;
   summary[0] = total;
   // ---- emit
-  const uint64_t limit = total < out_cap ? total : out_cap;
-  const uint64_t n_chunks = (limit + chunk - 1) / chunk;
   const pack::View table{ob, nullptr, nullptr, nullptr, 0, k, total};
   const CheckedSource src(cols, C, reinterpret_cast<const uint8_t*>(sep), sep_len, &stage, k);
   bool left_range = false;
-  std::vector<uint8_t> got;
-  for (uint64_t c = 0; c < n_chunks; c++) {
-    const uint64_t c0 = c * chunk;
-    const uint64_t c1 = c0 + chunk < limit ? c0 + chunk : limit;
-    const uint64_t j0 = pack::chunk_first_row(table, k, c0);
-    const uint64_t e = pack::chunk_end_row(table, k, 0, c1);
-    const uint64_t j1 = e > j0 ? e : j0;
-    if (j1 > k) return -1;
-    const Made m = make_chunk(src, table, j0, j1, sep_len, static_cast<uint32_t>(pad), static_cast<uint32_t>(fill), c0, c1, chunk, &got);
-    summary[4]++;
+  const long chunks = walk_chunks(table, k, total, chunk, out, out_cap, [&](uint64_t c0, uint64_t c1, uint64_t j0, uint64_t j1, std::vector<uint8_t>* got) {
+    const Made m = make_chunk(src, table, j0, j1, sep_len, static_cast<uint32_t>(pad), static_cast<uint32_t>(fill), c0, c1, chunk, got);
     summary[5] += m.streamed, summary[6] += m.from_image, summary[7] += m.used_stream;
     twice |= m.twice, left_range |= m.left_range;
-    for (uint64_t p = c0; p < c1; p += pack::kGroupBytes) {   // (each group of the chunk is stored once: the chunks partition [0, limit))
-      uint32_t w[4] = {0, 0, 0, 0};
-      for (uint64_t b = 0; b < pack::kGroupBytes && p + b < c1; b++) w[b >> 2] |= static_cast<uint32_t>(got[p - c0 + b]) << (8 * (b & 3));
-      if (!store_group(out, 0, p, limit, out_cap, w)) return -1;
-    }
-  }
+  });
+  if (chunks < 0) return -1;
+  summary[4] = static_cast<uint64_t>(chunks);
   return left_range || twice ? -1 : 0;
 }
 

@@ -272,6 +272,30 @@ def test_the_call_contract(rj, scan):
     assert err.value.status == RJ_BAD_ARGUMENT and "line break" in err.value.message
 
 
+def test_the_tail_store_under_an_out_cap_sweep(rj, scan):
+    """an output of two chunks and 21 bytes, fields of every tier, the last row's last field one that streams: below
+    min(out_cap, total) the reference's bytes, at and beyond it the sentinel, and the total returned whatever out_cap is"""
+    target = 2 * fc.EMIT_CHUNK + 21
+    kinds = [b"ab", b'q"r', b"", b"x" * 40, b'y"' * 20, b"c,d"]
+    values = [[kinds[(j + c) % len(kinds)] for j in range(400)] for c in range(2)]
+    values[1] = [b"z" * 40] * 400
+    rows = fc.lines(values)
+    k = max(n for n in range(1, 401) if sum(len(r) + 1 for r in rows[:n]) <= target)
+    lead = target - sum(len(r) + 1 for r in rows[:k])
+    values = [col[:k] for col in values]
+    cols = [Col(t) for t in columns_of(values, 17)]
+    text, begins, ends = fc.layout(rows[:k], 0x2C, lead, 1)
+    total = len(text)
+    assert total == target and k > 60
+    args = [c.arg() for c in cols]
+    for cap in (1, 15, 16, 17, 4095, 4096, 4097, total - 17, total - 16, total - 1, total, total + 16):
+        got, out, gb, ge = format_poisoned(rj, scan, args, fill=0x2C, lead=lead, cap=cap)
+        below = min(cap, total)
+        assert got == total, (cap, got, rj.load_library().rj_last_error())
+        assert out[:below] == text[:below] and out[below:] == bytes([POISON8]) * (cap + ROOM_BYTES - below), cap
+        assert (gb[:k] == begins).all() and (ge[:k] == ends).all(), cap
+
+
 def test_the_python_interface(rj, scan):
     import torch
     values = fc.random_rows(500, 3, 5, upto=12)

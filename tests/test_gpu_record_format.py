@@ -196,6 +196,58 @@ def test_the_output_passes_one_turn_of_the_emit_grid(rj, scan):
     assert (gb[:k] == np.arange(k) * (24 + gap)).all() and (ge[:k] == gb[:k] + 24).all()
 
 
+# ------------------------------------------------------------------------------------------------ the chunk's seam, the row loop, the tail store
+INT64_MIN_WORD = 1 << 63          # -9223372036854775808: the 20 bytes of the longest integer row
+
+
+def test_every_cut_of_a_row_by_a_chunk_seam(rj, scan):
+    """300 rows of 20 bytes at a pitch of 20 and of 21: for every i in 0..24 a lead that makes a row begin at 4096 - i, so the seam
+    cuts a row at every one of its bytes, falls on its begin and its end, and in the gap behind it"""
+    k, words = 300, [INT64_MIN_WORD] * 300
+    assert fc.text_of(INT64_MIN_WORD, fc.INT64) == b"-9223372036854775808"
+    d = dev_words(words)
+    for gap in (0, 1):
+        pitch = 20 + gap
+        for i in range(25):
+            lead = (4096 - i) % pitch
+            text, begins, ends = fc.layout(words, fc.INT64, None, None, 0x2C, lead, gap)
+            assert 4096 - i in begins and len(text) > 4096 + 24
+            total, out, gb, ge = format_poisoned(rj, scan, d, k, fc.INT64, fill=0x2C, lead=lead, gap=gap, cap=len(text))
+            assert total == len(text), (i, gap, total, rj.load_library().rj_last_error())
+            assert out[:total] == text and out[total:] == bytes([POISON8]) * ROOM_BYTES, (i, gap, out[4096 - 48:4096 + 24])
+            assert (gb[:k] == begins).all() and (ge[:k] == ends).all(), (i, gap)
+
+
+def test_more_than_256_empty_rows_inside_one_chunk(rj, scan):
+    """600 rows, rows 150..449 with a status that is not OK, gap 0: one chunk holds 300 empty rows and the rows around them, and
+    the lanes take its rows in two trips"""
+    k = 600
+    words = [(j * 7919 + 1) % (1 << 40) for j in range(k)]
+    status = [fc.NOT_OK[j % 4] if 150 <= j < 450 else fc.OK for j in range(k)]
+    text, begins, ends = fc.layout(words, fc.INT64, status, None, 10, 0, 0)
+    assert len(text) < 4096 and begins[150] == begins[450] == ends[449]
+    total, out, gb, ge = format_poisoned(rj, scan, dev_words(words), k, fc.INT64, dev(status, np.uint8), gap=0, cap=len(text))
+    assert total == len(text), (total, rj.load_library().rj_last_error())
+    assert out[:total] == text and out[total:] == bytes([POISON8]) * ROOM_BYTES
+    assert (gb[:k] == begins).all() and (ge[:k] == ends).all()
+
+
+def test_the_tail_store_under_an_out_cap_sweep(rj, scan):
+    """an output of two chunks and 21 bytes: below min(out_cap, total) the reference's bytes, at and beyond it the sentinel, and
+    the total returned whatever out_cap is"""
+    k, words = 391, [INT64_MIN_WORD] * 391
+    text, begins, ends = fc.layout(words, fc.INT64, None, None, 0x2C, 2, 1)
+    total = len(text)
+    assert total == 2 * 4096 + 21
+    d = dev_words(words)
+    for cap in (1, 15, 16, 17, 4095, 4096, 4097, total - 17, total - 16, total - 1, total, total + 16):
+        got, out, gb, ge = format_poisoned(rj, scan, d, k, fc.INT64, fill=0x2C, lead=2, gap=1, cap=cap)
+        below = min(cap, total)
+        assert got == total, (cap, got, rj.load_library().rj_last_error())
+        assert out[:below] == text[:below] and out[below:] == bytes([POISON8]) * (cap + ROOM_BYTES - below), cap
+        assert (gb[:k] == begins).all() and (ge[:k] == ends).all(), cap
+
+
 # ------------------------------------------------------------------------------------------------ edges and refusals
 def test_no_rows(rj, scan, columns):
     import torch

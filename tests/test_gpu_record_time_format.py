@@ -169,6 +169,23 @@ def test_more_than_256_empty_rows_inside_one_chunk(rj, scan):
     assert len(tf.layout(values, tf.CLF, tf.SECOND, status, None, 60, 10, 3, 0)[0]) == 3 + 12 * 26
 
 
+def test_the_tail_store_under_an_out_cap_sweep(rj, scan):
+    """an output of two chunks and 21 bytes: below min(out_cap, total) the reference's bytes, at and beyond it the sentinel, and
+    the total returned whatever out_cap is"""
+    k = 391
+    values = (np.random.RandomState(11).randint(0, 4 * 10 ** 9, k).astype(np.int64)).tolist()
+    text, begins, ends, counts = tf.layout(values, tf.ISO, tf.SECOND, None, None, 0, 0x2C, 2, 1)
+    total = len(text)
+    assert total == 2 * 4096 + 21 and counts[tf.OK] == k
+    d = dev(values)
+    for cap in (1, 15, 16, 17, 4095, 4096, 4097, total - 17, total - 16, total - 1, total, total + 16):
+        got, out, gb, ge, stats = format_poisoned(rj, scan, d, k, tf.ISO, tf.SECOND, fill=0x2C, lead=2, gap=1, cap=cap)
+        below = min(cap, total)
+        assert got == total, (cap, got, rj.load_library().rj_last_error())
+        assert out[:below] == text[:below] and out[below:] == bytes([POISON8]) * (cap + ROOM_BYTES - below), cap
+        assert (gb[:k] == begins).all() and (ge[:k] == ends).all() and stats == [k, 0, 0], cap
+
+
 def test_more_than_one_pass_of_both_grids(rj, scan):
     """262 465 rows at a pitch of 33 bytes: the check and the plan take their units round again, and the output passes the 8 MiB
     of one turn of the emit.  The ISO-shaped rows are compared in bulk with numpy.datetime_as_string over datetime64[s]; a

@@ -341,6 +341,27 @@ def test_out_too_small_the_size_query_and_out_given(rj, scan):
         assert (ge == POISON).all() if not kw.get("with_end", True) else (ge[:900] == ends).all()
 
 
+def test_the_tail_store_under_an_out_cap_sweep(rj, scan):
+    """an output of two chunks and 21 bytes whose last row ends in a piece that streams: below min(out_cap, total) the reference's
+    bytes, at and beyond it the sentinel, and the total returned whatever out_cap is"""
+    target = 2 * EMIT_CHUNK + 21
+    tables = [random_table(400, (0, 2, 9, 40), 140), zc.table([40] * 400, 141)]
+    rows = zc.lines([zc.pieces(*t) for t in tables], b" ", [7, 0], 32)
+    k = max(n for n in range(1, 401) if sum(len(r) + 1 for r in rows[:n]) <= target)
+    lead = target - sum(len(r) + 1 for r in rows[:k])
+    cols = [Col((t[0], t[1][:k], t[2][:k])) for t in tables]
+    text, begins, ends = zc.layout(rows[:k], 0x2C, lead, 1)
+    total = len(text)
+    assert total == target and k > 100 and len(rows[k - 1]) >= 40 >= STREAM_BYTES
+    args = [c.arg() for c in cols]
+    for cap in (1, 15, 16, 17, 4095, 4096, 4097, total - 17, total - 16, total - 1, total, total + 16):
+        got, out, gb, ge = zip_poisoned(rj, scan, args, [7, 0], b" ", fill=0x2C, lead=lead, cap=cap)
+        below = min(cap, total)
+        assert got == total, (cap, got, rj.load_library().rj_last_error())
+        assert out[:below] == text[:below] and out[below:] == bytes([POISON8]) * (cap + ROOM_BYTES - below), cap
+        assert (gb[:k] == begins).all() and (ge[:k] == ends).all(), cap
+
+
 def test_refusals_write_nothing(rj, scan):
     import torch
     lib = rj.load_library()
