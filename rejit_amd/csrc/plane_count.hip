@@ -43,6 +43,7 @@
 #include "exact_count.h"
 #include "kernels.h"
 #include "plane_codes.h"
+#include "plane_network.h"
 #include "short_walk.h"
 #include "stream_load.h"
 #include "wave_ops.h"
@@ -65,8 +66,45 @@ constexpr uint32_t kRing = RJ_PC_RING;       // candidate slots per wave; consum
 
 // the codes of 16 bytes: bits 2k, 2k + 1 = byte k
 __device__ __forceinline__ uint32_t codes16(const uint4& v, const PlaneCodes& k) {
-  const uint32_t s = k.shift;
-  return (codes4(v.x, k) >> s) | (codes4(v.y, k) << (8 - s)) | (codes4(v.z, k) << (16 - s)) | (codes4(v.w, k) << (24 - s));
+  return join_codes16(codes4(v.x, k), codes4(v.y, k), codes4(v.z, k), codes4(v.w, k), k.shift);
+}
+
+// ... of a lane's two pieces, as the streaming loop computes them: ONE statement of 24 instructions.  Eight masks, eight dot
+// products, and the two joins (a shift and three v_lshl_or_b32 each) taken in turns -- every v_dot4 stands at least six
+// instructions before the one that reads its result (gfx950 asks for three wait states there).  Written out because the compiler
+// (a) joins four parts with two shifts, a v_lshl_or and a v_or3, five operations where the chain needs four, and (b) puts an
+// s_nop in front of every empty asm statement that would keep the chain a chain: it has to assume the worst of a statement
+// it cannot read, and sixteen of them per turn of the loop cost more than the chain saved.
+__device__ __forceinline__ void codes16_pair(const uint4& va, const uint4& vb, const PlaneCodes& k, uint32_t& ca, uint32_t& cb) {
+  const uint32_t s = k.shift, up8 = 8 - s, up16 = 16 - s, up24 = 24 - s;
+  uint32_t a1, a2, a3, b1, b2, b3;
+  asm volatile("v_and_b32 %[ca], %[m], %[ax]\n"
+      "v_and_b32 %[a1], %[m], %[ay]\n"
+      "v_and_b32 %[a2], %[m], %[az]\n"
+      "v_and_b32 %[a3], %[m], %[aw]\n"
+      "v_and_b32 %[cb], %[m], %[bx]\n"
+      "v_and_b32 %[b1], %[m], %[by]\n"
+      "v_and_b32 %[b2], %[m], %[bz]\n"
+      "v_and_b32 %[b3], %[m], %[bw]\n"
+      "v_dot4_u32_u8 %[ca], %[ca], %[w], 0\n"
+      "v_dot4_u32_u8 %[a1], %[a1], %[w], 0\n"
+      "v_dot4_u32_u8 %[a2], %[a2], %[w], 0\n"
+      "v_dot4_u32_u8 %[a3], %[a3], %[w], 0\n"
+      "v_dot4_u32_u8 %[cb], %[cb], %[w], 0\n"
+      "v_dot4_u32_u8 %[b1], %[b1], %[w], 0\n"
+      "v_dot4_u32_u8 %[b2], %[b2], %[w], 0\n"
+      "v_dot4_u32_u8 %[b3], %[b3], %[w], 0\n"
+      "v_lshrrev_b32 %[ca], %[s], %[ca]\n"
+      "v_lshrrev_b32 %[cb], %[s], %[cb]\n"
+      "v_lshl_or_b32 %[ca], %[a1], %[u8], %[ca]\n"
+      "v_lshl_or_b32 %[cb], %[b1], %[u8], %[cb]\n"
+      "v_lshl_or_b32 %[ca], %[a2], %[u16], %[ca]\n"
+      "v_lshl_or_b32 %[cb], %[b2], %[u16], %[cb]\n"
+      "v_lshl_or_b32 %[ca], %[a3], %[u24], %[ca]\n"
+      "v_lshl_or_b32 %[cb], %[b3], %[u24], %[cb]"
+      : [ca] "=&v"(ca), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [cb] "=&v"(cb), [b1] "=&v"(b1), [b2] "=&v"(b2), [b3] "=&v"(b3)
+      : [ax] "v"(va.x), [ay] "v"(va.y), [az] "v"(va.z), [aw] "v"(va.w), [bx] "v"(vb.x), [by] "v"(vb.y), [bz] "v"(vb.z), [bw] "v"(vb.w),
+        [m] "s"(k.cmask), [w] "s"(0x40100401u), [s] "s"(s), [u8] "s"(up8), [u16] "s"(up16), [u24] "s"(up24));
 }
 
 struct Raw {
@@ -107,10 +145,13 @@ __device__ __forceinline__ uint32_t guarded_dword(const uint8_t* text, uint64_t 
 template <int NB, bool COLD>
 __device__ __forceinline__ uint32_t plane_test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const PlaneCountParams& a) {
   constexpr uint32_t kEven = 0x55555555u;
-  const uint32_t L = (ta & kEven) | ((tb << 1) & ~kEven);
-  const uint32_t H = ((ta >> 1) & kEven) | (tb & ~kEven);
-  const uint32_t Ln = (ha & kEven) | ((hb << 1) & ~kEven);
-  const uint32_t Hn = ((ha >> 1) & kEven) | (hb & ~kEven);
+  // (0xCA: x ? y : z, the even bits from y and the odd bits from z.  As the instruction itself: written `(ta & kEven) | ((tb << 1)
+  // & ~kEven)` the compiler sees the two masked halves and forms every plane from the halves -- eight v_and_b32 with 0x55555555 /
+  // 0xaaaaaaaa per block beside the four selects)
+  const uint32_t L = bitop3<0xCA>(kEven, ta, tb << 1);
+  const uint32_t H = bitop3<0xCA>(kEven, ta >> 1, tb);
+  const uint32_t Ln = bitop3<0xCA>(kEven, ha, hb << 1);
+  const uint32_t Hn = bitop3<0xCA>(kEven, ha >> 1, hb);
   // The four CODE planes (bit = the position's symbol has code c) of the 32 positions and of the 32 that follow.  "Window byte
   // i of base b fits at position p" is then ONE shifted plane -- alignbit(next[c], here[c], 2 i), c = the code of the base's
   // byte i -- where two bit planes compared against the base's masks took a shift each (shared by the bases), an XOR and a
@@ -137,7 +178,7 @@ __device__ __forceinline__ uint32_t plane_test(uint32_t ta, uint32_t tb, uint32_
   // (wave-uniform launch constants: sixteen scalar bit-field extracts, made once per wave and kept in scalar registers across the
   // streaming loop)
   auto code = [&](int b, int i) { return (codes >> (16 * b + 2 * i)) & 3u; };
-  uint32_t E[8][NB], Z[NB], O[NB];
+  uint32_t E[8][NB], O[NB];
 #pragma unroll
   for (int half = 0; half < 2; half++) {
     // (the picks of four window bytes in one statement: nothing but the indexed reads runs under the index mode)
@@ -214,22 +255,10 @@ __device__ __forceinline__ uint32_t plane_test(uint32_t ta, uint32_t tb, uint32_
           : [c40] "s"(code(0, 4)), [c41] "s"(code(1, 4)), [c50] "s"(code(0, 5)), [c51] "s"(code(1, 5)), [c60] "s"(code(0, 6)), [c61] "s"(code(1, 6)), [c70] "s"(code(0, 7)), [c71] "s"(code(1, 7)), "v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(n0), "v"(n1), "v"(n2), "v"(n3));
       }
     }
-#pragma unroll
-    for (int i = 4 * half; i < 4 * half + 4; i++)
-#pragma unroll
-      for (int b = 0; b < NB; b++) {
-        const uint32_t e = E[i][b];
-        if (i == 0) {
-          Z[b] = e;
-        } else if (i == 1) {
-          O[b] = Z[b] | e;
-          Z[b] &= e;
-        } else {
-          O[b] = Z[b] | (O[b] & e);
-          if (i < 7) Z[b] &= e;
-        }
-      }
   }
+  // at most one of a base's eight window bytes does not fit (plane_network.h: nine three-input operations per base, four deep)
+#pragma unroll
+  for (int b = 0; b < NB; b++) O[b] = at_most_one_miss(E[0][b], E[1][b], E[2][b], E[3][b], E[4][b], E[5][b], E[6][b], E[7][b]);
   return NB > 1 ? (O[0] | O[NB - 1]) : O[0];
 }
 
@@ -321,10 +350,13 @@ namespace {
 template <bool TOL>
 __device__ __forceinline__ uint32_t general_test(uint32_t ta, uint32_t tb, uint32_t ha, uint32_t hb, const PlaneCountGParams& g) {
   constexpr uint32_t kEven = 0x55555555u;
-  const uint32_t L = (ta & kEven) | ((tb << 1) & ~kEven);
-  const uint32_t H = ((ta >> 1) & kEven) | (tb & ~kEven);
-  const uint32_t Ln = (ha & kEven) | ((hb << 1) & ~kEven);
-  const uint32_t Hn = ((ha >> 1) & kEven) | (hb & ~kEven);
+  // (0xCA: x ? y : z, the even bits from y and the odd bits from z.  As the instruction itself: written `(ta & kEven) | ((tb << 1)
+  // & ~kEven)` the compiler sees the two masked halves and forms every plane from the halves -- eight v_and_b32 with 0x55555555 /
+  // 0xaaaaaaaa per block beside the four selects)
+  const uint32_t L = bitop3<0xCA>(kEven, ta, tb << 1);
+  const uint32_t H = bitop3<0xCA>(kEven, ta >> 1, tb);
+  const uint32_t Ln = bitop3<0xCA>(kEven, ha, hb << 1);
+  const uint32_t Hn = bitop3<0xCA>(kEven, ha >> 1, hb);
   register uint32_t q0 asm("v48") = ~(L | H);
   register uint32_t q1 asm("v49") = L & ~H;
   register uint32_t q2 asm("v50") = ~L & H;
@@ -362,21 +394,7 @@ __device__ __forceinline__ uint32_t general_test(uint32_t ta, uint32_t tb, uint3
         : [i0] "s"(ix[0]), [i1] "s"(ix[1]), [i2] "s"(ix[2]), [i3] "s"(ix[3]), [i4] "s"(ix[4]), [i5] "s"(ix[5]), [i6] "s"(ix[6]), [i7] "s"(ix[7]), "v"(q0), "v"(q1), "v"(q2),
           "v"(q3), "v"(q4), "v"(n0), "v"(n1), "v"(n2), "v"(n3), "v"(n4));
     if (TOL) {
-      // Z: no code differs so far; O: at most one does
-      uint32_t Z = e0, O = e0 | e1;
-      Z &= e1;
-      O = Z | (O & e2);
-      Z &= e2;
-      O = Z | (O & e3);
-      Z &= e3;
-      O = Z | (O & e4);
-      Z &= e4;
-      O = Z | (O & e5);
-      Z &= e5;
-      O = Z | (O & e6);
-      Z &= e6;
-      O = Z | (O & e7);
-      c |= O;
+      c |= at_most_one_miss(e0, e1, e2, e3, e4, e5, e6, e7);   // at most one code differs
     } else {
       const uint32_t z0 = e0 & e1 & e2, z1 = e3 & e4 & e5;
       c |= z0 & z1 & e6 & e7;
@@ -799,7 +817,8 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
   }
   __syncthreads();
   if (c < fast_end) {
-    uint32_t xa = codes16(ra.a, k), xb = codes16(ra.b, k);   // block c
+    uint32_t xa, xb;
+    codes16_pair(ra.a, ra.b, k, xa, xb);   // block c
     stash_put(0, ra);
     if (S::kCapture) __builtin_amdgcn_sched_barrier(0);   // (the stash is written before the buffer is loaded again)
     load_block(blk(c + 2), lane_rel, ra);
@@ -808,10 +827,11 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
     // (ahead: block c + 3, a scalar pointer that advances with the loop; block c + 4 is its immediate offset)
     const uint8_t* ahead = a.text + (static_cast<uint64_t>(c) + 3) * kBlock;
     while (c + 1 < fast_end) {
-      const uint32_t ya = codes16(rb.a, k), yb = codes16(rb.b, k);   // block c + 1
+      uint32_t ya, yb;
+      codes16_pair(rb.a, rb.b, k, ya, yb);   // block c + 1
       // (the codes must exist BEFORE the buffer is loaded again: when the compiler sinks their computation towards its
-      // use, the reload lands in other registers and is copied back at the loop's end -- behind a wait for it)
-      asm volatile("" ::"v"(ya), "v"(yb));
+      // use, the reload lands in other registers and is copied back at the loop's end -- behind a wait for it.  codes16_pair
+      // is a volatile statement, and so is the one load_block begins with: they keep their order)
       stash_put(1, rb);
       if (S::kCapture) __builtin_amdgcn_sched_barrier(0);
       if (c + 3 <= last_own) load_block(ahead, lane_rel, rb);
@@ -823,9 +843,7 @@ __global__ __launch_bounds__(256) void plane_count(typename S::Args g) {
         push_block<S::kList, S::kCapture>(w, hm, lane_rel, (c - c0) * static_cast<uint32_t>(kBlock), 0u);
       }
       __builtin_amdgcn_sched_barrier(0);
-      xa = codes16(ra.a, k);   // block c + 2 (stale bytes when c + 2 == fast_end: not used then)
-      xb = codes16(ra.b, k);
-      asm volatile("" ::"v"(xa), "v"(xb));
+      codes16_pair(ra.a, ra.b, k, xa, xb);   // block c + 2 (stale bytes when c + 2 == fast_end: not used then)
       if (c + 2 < fast_end) stash_put(0, ra);
       else follower_put(0, behind.x, behind.y);   // (the span's last fast block: `behind` stands in for block c + 2)
       if (S::kCapture) __builtin_amdgcn_sched_barrier(0);
