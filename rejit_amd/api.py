@@ -456,7 +456,7 @@ class Program:
     def info(self) -> dict:
         i = _Info()
         _check(self._lib.rj_program_info(self._h, ctypes.byref(i)))
-        return {k: int(getattr(i, k)) for k, _ in _Info._fields_}
+        return _stats_dict(i)
 
     # host-text entry points (the four JIT function pointers of the reference)
     def match_all(self, text: bytes) -> List[Tuple[int, int]]:
@@ -476,12 +476,16 @@ class Program:
         counts = (ctypes.c_uint64 * k)()
         spans = _u64p()
         total = _check(self._lib.rj_match_all_batch(self._h, arr, sizes, k, counts, ctypes.byref(spans)))
+        return self._take_spans(counts, k, spans, total)
+
+    def _take_spans(self, counts, k, spans, total) -> List[List[Tuple[int, int]]]:
+        """a counted span list of the library's as one list of pairs per text; the library's list is freed"""
         out, at = [], 0
         for i in range(k):
             c = int(counts[i])
             out.append([(int(spans[2 * (at + j)]), int(spans[2 * (at + j) + 1])) for j in range(c)])
             at += c
-        assert at == total
+        assert at == total, (at, total)
         if total:
             self._lib.rj_free_spans(spans)
         return out
@@ -489,15 +493,7 @@ class Program:
     def match_all_batch_counts(self, texts: List[bytes]) -> List[int]:
         """rj_match_all_batch as a native caller pays for it -- the spans DO cross PCIe and are handed out -- but
         without turning them into Python tuples: the per-text counts only (bench.py's jrep extra: 10^8 line starts)."""
-        k = len(texts)
-        arr = (ctypes.c_char_p * k)(*texts)
-        sizes = (ctypes.c_size_t * k)(*[len(t) for t in texts])
-        counts = (ctypes.c_uint64 * k)()
-        spans = _u64p()
-        total = _check(self._lib.rj_match_all_batch(self._h, arr, sizes, k, counts, ctypes.byref(spans)))
-        if total:
-            self._lib.rj_free_spans(spans)
-        return [int(counts[i]) for i in range(k)]
+        return [int(c) for c in self.match_all_batch_table(self.batch_table(texts))]
 
     def batch_table(self, texts: List[bytes]):
         """The caller's file table for rj_match_all_batch -- the arrays of pointers and sizes a native caller holds anyway
@@ -531,15 +527,7 @@ class Program:
         counts = (ctypes.c_uint64 * max(k, 1))()
         spans = _u64p()
         total = _check(self._lib.rj_match_all_packed(self._h, ctypes.c_void_p(buf_ptr), off, sz_, k, total_bytes, counts, ctypes.byref(spans)))
-        out, at = [], 0
-        for i in range(k):
-            c = int(counts[i])
-            out.append([(int(spans[2 * (at + j)]), int(spans[2 * (at + j) + 1])) for j in range(c)])
-            at += c
-        assert at == total, (at, total)
-        if total:
-            self._lib.rj_free_spans(spans)
-        return out
+        return self._take_spans(counts, k, spans, total)
 
     def count(self, text: bytes) -> int:
         """Regej::MatchAllCount: rj_match_all with a NULL span list."""
@@ -582,6 +570,132 @@ class Program:
         return bool(_check(self._lib.rj_match_full(self._h, text, len(text))))
 
 
+# The argument layer of Scan's record calls: the host protocol they share, each piece once.  A record method is
+# its own argument checks, one `call` closure that lists the C arguments in include/rejit_hip.h's order, and its result.
+
+def _ptr(x):
+    """the pointer of a tensor as a C argument: NULL for None and for an empty tensor"""
+    return ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
+
+
+def _stream(device, stream):
+    """stream=None: the device's current stream"""
+    import torch
+
+    return torch.cuda.current_stream(device).cuda_stream if stream is None else stream
+
+
+def _check_text(t, device=None):
+    import torch
+
+    assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda and (device is None or t.device == device)
+
+
+def _check_column(x, dtype, device, n):
+    assert x.dtype == dtype and x.is_contiguous() and x.device == device and x.numel() == n
+
+
+def _check_table(rec_begin, rec_end, device) -> int:
+    """-> n_records"""
+    import torch
+
+    n_records = int(rec_begin.numel())
+    _check_column(rec_begin, torch.int64, device, n_records)
+    _check_column(rec_end, torch.int64, device, n_records)
+    return n_records
+
+
+def _rows(indices, every, device):
+    """A row list -> (the tensor to pass, k).  None: every row.  The caller keeps the tensor until the library has returned."""
+    import torch
+
+    if indices is None:
+        return None, every
+    assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == device
+    if indices.numel() == 0:
+        return torch.zeros(1, dtype=torch.int64, device=device), 0   # (a non-null pointer: NULL means every record)
+    return indices, int(indices.numel())
+
+
+def _stats_dict(s) -> dict:
+    return {f: int(getattr(s, f)) for f, _ in s._fields_}
+
+
+def _sized_text(call, out, device, name, noun):
+    """A new device text through call(buf, cap) -> total.  Without `out` ONE size query, exactly `total` bytes allocated and
+    filled (no second call for an empty text); with `out` one call into it, RejitError when it is too small, else out[:total]."""
+    import torch
+
+    if out is None:
+        total = call(None, 0)
+        out = torch.empty(total, dtype=torch.uint8, device=device)
+        if total:
+            call(out, total)
+        return out
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == device
+    cap = int(out.numel())
+    total = call(out if cap else None, cap)
+    if total > cap:
+        raise RejitError(-4, "%s: %s has %d bytes, `out` %d" % (name, noun, total, cap))
+    return out[:total]
+
+
+def _fill_byte(fill, program, name) -> int:
+    """fill=None: the pattern's batch separator"""
+    if fill is not None:
+        return int(fill)
+    fill = program.batch_separator()
+    if fill < 0:
+        raise RejitError(-4, "%s: the pattern has no batch separator (it is matched text by text): pass fill" % name)
+    return fill
+
+
+def _one_byte(x, name, what) -> int:
+    """an int, or bytes of length one"""
+    if isinstance(x, int):
+        return int(x)
+    if len(bytes(x)) != 1:
+        raise ValueError("%s: %s is not one byte" % (name, what))
+    return bytes(x)[0]
+
+
+def _zip_columns(columns, widths, name):
+    """The rj_zip_column array of (text, rec_begin, rec_end[, indices]) columns -> (array, k, the tensors it points into).  An
+    absent row list is pointer 0 and n_indices 0, an empty one _rows' dummy and 0."""
+    if not columns:
+        raise RejitError(-4, "%s: no columns (a call takes 1 to 16)" % name)
+    device = columns[0][0].device
+    cols = (ZipColumn * len(columns))()
+    keep = []
+    for c, column in enumerate(columns):
+        if len(column) not in (3, 4):
+            raise ValueError("%s: a column is (text, rec_begin, rec_end) or (text, rec_begin, rec_end, indices)" % name)
+        t, rec_begin, rec_end = column[:3]
+        _check_text(t, device)
+        n_records = _check_table(rec_begin, rec_end, device)
+        indices, rows = _rows(column[3] if len(column) == 4 else None, n_records, device)
+        keep.append((t, rec_begin, rec_end, indices))
+        cols[c] = ZipColumn(_ptr(t).value, int(t.numel()), _ptr(rec_begin).value, _ptr(rec_end).value, n_records, _ptr(indices).value,
+                            0 if indices is None else rows, widths[c], 0)
+        if c == 0:
+            k = rows
+    return cols, k, keep
+
+
+def _parse_rows(call, t, rec_begin, rec_end, indices, dtype, stats, stream):
+    """parse_records and parse_time_records behind their own checks: call(n_records, indices, k, values, status, stats, stream) is
+    the library call"""
+    import torch
+
+    n_records = _check_table(rec_begin, rec_end, t.device)
+    indices, k = _rows(indices, n_records, t.device)
+    values = torch.empty(k, dtype=dtype, device=t.device)
+    status = torch.empty(k, dtype=torch.uint8, device=t.device)
+    out = _ParseStats()
+    _check(call(n_records, indices, k, values, status, ctypes.byref(out) if stats else None, ctypes.c_void_p(_stream(t.device, stream))))
+    return (values, status, _stats_dict(out)) if stats else (values, status)
+
+
 class Scan:
     """Device-resident scanning (rj_scan): text stays in HBM, results stay in HBM."""
 
@@ -615,11 +729,8 @@ class Scan:
         return int(_check(self._lib.rj_scan_count(self._h, ctypes.c_void_p(d_text_ptr), n, ctypes.c_void_p(stream))))
 
     def count_tensor(self, t, n: Optional[int] = None, stream=None) -> int:
-        import torch
-
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
-        return self.count(t.data_ptr(), int(t.numel() if n is None else n), stream=st)
+        _check_text(t)
+        return self.count(t.data_ptr(), int(t.numel() if n is None else n), stream=_stream(t.device, stream))
 
     def gather_spans(self, d_text_ptr: int, n: int, offset: int, rank: int, world: int, root: int = 0, comm: Optional[int] = None,
                      allgather=None, gatherv=None, own_begin: int = 0, own_end: Optional[int] = None, stream: int = 0):
@@ -651,11 +762,8 @@ class Scan:
 
     def run_tensor(self, t, n: Optional[int] = None, stream=None, **kw) -> int:
         """t: a contiguous uint8 torch tensor on the GPU."""
-        import torch
-
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
-        return self.run(t.data_ptr(), int(t.numel() if n is None else n), stream=st, **kw)
+        _check_text(t)
+        return self.run(t.data_ptr(), int(t.numel() if n is None else n), stream=_stream(t.device, stream), **kw)
 
     def run_records(self, text_tensor, rec_begin, rec_end, counts=None, first=None, stream=None) -> RecordsResult:
         """rj_scan_records: one whole-text run over `text_tensor` (contiguous uint8 on the GPU), its matches handed to the
@@ -665,21 +773,18 @@ class Scan:
         import torch
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        k = int(rec_begin.numel())
-        for x in (rec_begin, rec_end):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == k
+        _check_text(t)
+        k = _check_table(rec_begin, rec_end, t.device)
         if counts is None:
             counts = torch.empty(k, dtype=torch.int32, device=t.device)
         if first is None:
             first = torch.empty(k, dtype=torch.int64, device=t.device)
-        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.device == t.device and counts.numel() == k
-        assert first.dtype == torch.int64 and first.is_contiguous() and first.device == t.device and first.numel() == k
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        _check_column(counts, torch.int32, t.device, k)
+        _check_column(first, torch.int64, t.device, k)
+        st = _stream(t.device, stream)
         rs = _RecordStats()
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if k else 0)
-        _check(self._lib.rj_scan_records(self._h, ctypes.c_void_p(t.data_ptr()), int(t.numel()), ptr(rec_begin), ptr(rec_end), k,
-                                         ptr(counts), ptr(first), ctypes.byref(rs), ctypes.c_void_p(st)))
+        _check(self._lib.rj_scan_records(self._h, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), k, _ptr(counts), _ptr(first), ctypes.byref(rs),
+                                         ctypes.c_void_p(st)))
         self._records = (t.device, k, counts, st)   # (the selection reads these counts: kept alive)
         return RecordsResult(rs, counts, first, k)
 
@@ -698,7 +803,7 @@ class Scan:
         room = k if cap is None else min(int(cap), k)
         out = torch.empty(max(room, 1), dtype=torch.int64, device=device)
         st = st0 if stream is None else stream
-        total = int(_check(self._lib.rj_scan_records_select(self._h, int(invert), ctypes.c_void_p(out.data_ptr()), room, ctypes.c_void_p(st))))
+        total = int(_check(self._lib.rj_scan_records_select(self._h, int(invert), _ptr(out), room, ctypes.c_void_p(st))))
         self.n_selected = total
         return out[:min(total, room)]
 
@@ -714,42 +819,18 @@ class Scan:
         import torch
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        n_records = int(rec_begin.numel())
-        for x in (rec_begin, rec_end):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
-        if fill is None:
-            fill = self.program.batch_separator()
-            if fill < 0:
-                raise RejitError(-4, "pack_records: the pattern has no batch separator (it is matched text by text): pass fill")
-        keep = None
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
-            k = int(indices.numel())
-            if k == 0:
-                keep = indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
-        else:
-            k = n_records
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        _check_text(t)
+        n_records = _check_table(rec_begin, rec_end, t.device)
+        fill = _fill_byte(fill, self.program, "pack_records")
+        indices, k = _rows(indices, n_records, t.device)
+        st = _stream(t.device, stream)
         out_begin = torch.empty(k, dtype=torch.int64, device=t.device)
         out_end = torch.empty(k, dtype=torch.int64, device=t.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
 
         def call(buf, cap):
-            return int(_check(self._lib.rj_scan_records_pack(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k,
-                                                             int(fill), int(lead), int(gap), ptr(buf) if cap else None, cap, ptr(out_begin), ptr(out_end),
-                                                             ctypes.c_void_p(st))))
-        if out is None:
-            total = call(None, 0)
-            out = torch.empty(total, dtype=torch.uint8, device=t.device)
-            if total:
-                call(out, total)
-            return out, out_begin, out_end
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == t.device
-        total = call(out, int(out.numel()))
-        if total > out.numel():
-            raise RejitError(-4, "pack_records: the packed text has %d bytes, `out` %d" % (total, out.numel()))
-        return out[:total], out_begin, out_end
+            return int(_check(self._lib.rj_scan_records_pack(self._h, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), n_records, _ptr(indices), k,
+                                                             fill, int(lead), int(gap), _ptr(buf), cap, _ptr(out_begin), _ptr(out_end), ctypes.c_void_p(st))))
+        return _sized_text(call, out, t.device, "pack_records", "the packed text"), out_begin, out_end
 
     def translate_records(self, text_tensor, rec_begin, rec_end, table=None, delete: bytes = b"", indices=None, fill=None, lead: int = 0, gap: int = 1,
                           out=None, stream=None, stats=False):
@@ -766,10 +847,8 @@ class Scan:
         from . import records as _records
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        n_records = int(rec_begin.numel())
-        for x in (rec_begin, rec_end):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
+        _check_text(t)
+        n_records = _check_table(rec_begin, rec_end, t.device)
         if table is not None:
             table = bytes(table)
             if len(table) != 256:
@@ -779,39 +858,19 @@ class Scan:
             drop = bytes(delete)
         elif delete:
             drop = bytes(_records.drop_set(delete))
-        if fill is None:
-            fill = self.program.batch_separator()
-            if fill < 0:
-                raise RejitError(-4, "translate_records: the pattern has no batch separator (it is matched text by text): pass fill")
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
-        else:
-            k = n_records
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        fill = _fill_byte(fill, self.program, "translate_records")
+        indices, k = _rows(indices, n_records, t.device)
+        st = _stream(t.device, stream)
         out_begin = torch.empty(k, dtype=torch.int64, device=t.device)
         out_end = torch.empty(k, dtype=torch.int64, device=t.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
         counts = _TranslateStats()
 
         def call(buf, cap):
-            return int(_check(self._lib.rj_scan_records_translate(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k,
-                                                                  table, drop, int(fill), int(lead), int(gap), ptr(buf) if cap else None, cap, ptr(out_begin),
-                                                                  ptr(out_end), ctypes.byref(counts) if stats else None, ctypes.c_void_p(st))))
-        result = lambda text: (text, out_begin, out_end) + (({f: int(getattr(counts, f)) for f, _ in _TranslateStats._fields_},) if stats else ())
-        if out is None:
-            total = call(None, 0)
-            out = torch.empty(total, dtype=torch.uint8, device=t.device)
-            if total:
-                call(out, total)
-            return result(out)
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == t.device
-        total = call(out, int(out.numel()))
-        if total > out.numel():
-            raise RejitError(-4, "translate_records: the translated text has %d bytes, `out` %d" % (total, out.numel()))
-        return result(out[:total])
+            return int(_check(self._lib.rj_scan_records_translate(self._h, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), n_records, _ptr(indices), k,
+                                                                  table, drop, fill, int(lead), int(gap), _ptr(buf), cap, _ptr(out_begin), _ptr(out_end),
+                                                                  ctypes.byref(counts) if stats else None, ctypes.c_void_p(st))))
+        text = _sized_text(call, out, t.device, "translate_records", "the translated text")
+        return (text, out_begin, out_end, _stats_dict(counts)) if stats else (text, out_begin, out_end)
 
     def csv_records(self, text_tensor, delimiter: bytes = b",", quote=b'"', rows: bool = True, stream=None, row_cap: Optional[int] = None,
                     field_cap: Optional[int] = None) -> CsvResult:
@@ -825,18 +884,16 @@ class Scan:
         import torch
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        byte = lambda x, name: x if isinstance(x, int) else (bytes(x)[0] if len(bytes(x)) == 1 else _raise(ValueError("csv_records: %s is not one byte" % name)))
-        d = byte(delimiter, "delimiter")
-        q = -1 if quote is None else byte(quote, "quote")
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        _check_text(t)
+        d = _one_byte(delimiter, "csv_records", "delimiter")
+        q = -1 if quote is None else _one_byte(quote, "csv_records", "quote")
+        st = _stream(t.device, stream)
         cs = _CsvStats()
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
 
         def call(tables, rcap, fcap):
             rf, rb, re, fb, fe, ff = tables
-            return int(_check(self._lib.rj_scan_records_csv(self._h, ptr(t), int(t.numel()), d, q, ptr(rf), ptr(rb), ptr(re), rcap, ptr(fb), ptr(fe), ptr(ff), fcap,
-                                                            ctypes.byref(cs), ctypes.c_void_p(st))))
+            return int(_check(self._lib.rj_scan_records_csv(self._h, _ptr(t), int(t.numel()), d, q, _ptr(rf), _ptr(rb), _ptr(re), rcap, _ptr(fb), _ptr(fe),
+                                                            _ptr(ff), fcap, ctypes.byref(cs), ctypes.c_void_p(st))))
         if row_cap is None or field_cap is None:
             call((None,) * 6, 0, 0)
             row_cap, field_cap = int(cs.n_rows), int(cs.n_fields)
@@ -848,7 +905,7 @@ class Scan:
         n_rows, n_fields = int(cs.n_rows), int(cs.n_fields)
         if n_rows > row_cap or n_fields > field_cap:
             raise RejitError(-4, "csv_records: the text has %d rows and %d fields, the caps were %d and %d" % (n_rows, n_fields, row_cap, field_cap))
-        stats = {f: int(getattr(cs, f)) for f, _ in _CsvStats._fields_}
+        stats = _stats_dict(cs)
         if stats["first_bad"] == (1 << 64) - 1:
             stats["first_bad"] = None
         rf, rb, re, fb, fe, ff = tables
@@ -866,44 +923,22 @@ class Scan:
         import torch
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        n_records = int(rec_begin.numel())
-        for x in (rec_begin, rec_end, result.first):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
-        assert result.counts.dtype == torch.int32 and result.counts.is_contiguous() and result.counts.device == t.device and result.counts.numel() == n_records
+        _check_text(t)
+        n_records = _check_table(rec_begin, rec_end, t.device)
+        _check_column(result.first, torch.int64, t.device, n_records)
+        _check_column(result.counts, torch.int32, t.device, n_records)
         repl = bytes(repl)
-        if fill is None:
-            fill = self.program.batch_separator()
-            if fill < 0:
-                raise RejitError(-4, "replace_records: the pattern has no batch separator (it is matched text by text): pass fill")
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
-        else:
-            k = n_records
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        fill = _fill_byte(fill, self.program, "replace_records")
+        indices, k = _rows(indices, n_records, t.device)
+        st = _stream(t.device, stream)
         out_begin = torch.empty(k, dtype=torch.int64, device=t.device)
         out_end = torch.empty(k, dtype=torch.int64, device=t.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
 
         def call(buf, cap):
-            return int(_check(self._lib.rj_scan_records_replace(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records,
-                                                                ptr(result.counts), ptr(result.first), ptr(indices), k, repl, len(repl), int(fill),
-                                                                int(lead), int(gap), ptr(buf) if cap else None, cap, ptr(out_begin), ptr(out_end),
-                                                                ctypes.c_void_p(st))))
-        if out is None:
-            total = call(None, 0)
-            out = torch.empty(total, dtype=torch.uint8, device=t.device)
-            if total:
-                call(out, total)
-            return out, out_begin, out_end
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == t.device
-        total = call(out, int(out.numel()))
-        if total > out.numel():
-            raise RejitError(-4, "replace_records: the new text has %d bytes, `out` %d" % (total, out.numel()))
-        return out[:total], out_begin, out_end
+            return int(_check(self._lib.rj_scan_records_replace(self._h, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), n_records,
+                                                                _ptr(result.counts), _ptr(result.first), _ptr(indices), k, repl, len(repl), fill, int(lead),
+                                                                int(gap), _ptr(buf), cap, _ptr(out_begin), _ptr(out_end), ctypes.c_void_p(st))))
+        return _sized_text(call, out, t.device, "replace_records", "the new text"), out_begin, out_end
 
     def split_records(self, rec_begin, rec_end, result: RecordsResult, n: int, indices=None, what: str = "between", stream=None):
         """rj_scan_records_split: the fields (what="between": the pieces between a record's own matches -- `awk -F RE`,
@@ -916,29 +951,21 @@ class Scan:
         run_records and pack_records.  RejitError (RJ_BAD_ARGUMENT, naming the first bad row) as replace_records."""
         import torch
 
-        n_records = int(rec_begin.numel())
         device = rec_begin.device
-        for x in (rec_begin, rec_end, result.first):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == device and x.numel() == n_records
-        assert result.counts.dtype == torch.int32 and result.counts.is_contiguous() and result.counts.device == device and result.counts.numel() == n_records
+        n_records = _check_table(rec_begin, rec_end, device)
+        _check_column(result.first, torch.int64, device, n_records)
+        _check_column(result.counts, torch.int32, device, n_records)
         if what not in ("between", "matches"):
             raise ValueError("split_records: what is 'between' or 'matches', not %r" % (what,))
         code = 0 if what == "between" else 1
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=device)   # (a non-null pointer: NULL means every record)
-        else:
-            k = n_records
-        st = torch.cuda.current_stream(device).cuda_stream if stream is None else stream
+        indices, k = _rows(indices, n_records, device)
+        st = _stream(device, stream)
         piece_first = torch.empty(k + 1, dtype=torch.int64, device=device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
 
         def call(pb, pe, cap):
-            return int(_check(self._lib.rj_scan_records_split(self._h, int(n), ptr(rec_begin), ptr(rec_end), n_records, ptr(result.counts),
-                                                              ptr(result.first), ptr(indices), k, code, ptr(piece_first), ptr(pb) if cap else None,
-                                                              ptr(pe) if cap else None, cap, ctypes.c_void_p(st))))
+            return int(_check(self._lib.rj_scan_records_split(self._h, int(n), _ptr(rec_begin), _ptr(rec_end), n_records, _ptr(result.counts),
+                                                              _ptr(result.first), _ptr(indices), k, code, _ptr(piece_first), _ptr(pb), _ptr(pe), cap,
+                                                              ctypes.c_void_p(st))))
         total = call(None, None, 0)
         piece_begin = torch.empty(total, dtype=torch.int64, device=device)
         piece_end = torch.empty(total, dtype=torch.int64, device=device)
@@ -957,24 +984,15 @@ class Scan:
         import torch
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        n_records = int(rec_begin.numel())
-        for x in (rec_begin, rec_end):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
-        else:
-            k = n_records
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        _check_text(t)
+        n_records = _check_table(rec_begin, rec_end, t.device)
+        indices, k = _rows(indices, n_records, t.device)
+        st = _stream(t.device, stream)
         group = torch.empty(k, dtype=torch.int64, device=t.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
 
         def call(g, rep, count, cap):
-            return int(_check(self._lib.rj_scan_records_group(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k,
-                                                              ptr(g), ptr(rep) if cap else None, ptr(count) if cap else None, cap, ctypes.c_void_p(st))))
+            return int(_check(self._lib.rj_scan_records_group(self._h, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), n_records, _ptr(indices), k,
+                                                              _ptr(g), _ptr(rep), _ptr(count), cap, ctypes.c_void_p(st))))
         total = call(group, None, None, 0)
         rep = torch.empty(total, dtype=torch.int64, device=t.device)
         count = torch.empty(total, dtype=torch.int64, device=t.device)
@@ -994,26 +1012,14 @@ class Scan:
         import torch
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        n_records = int(rec_begin.numel())
-        for x in (rec_begin, rec_end):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
-        else:
-            k = n_records
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        _check_text(t)
+        n_records = _check_table(rec_begin, rec_end, t.device)
+        indices, k = _rows(indices, n_records, t.device)
         order = torch.empty(k, dtype=torch.int64, device=t.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
         out = _SortStats()
-        _check(self._lib.rj_scan_records_sort(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k, ptr(order),
-                                              ctypes.byref(out), ctypes.c_void_p(st)))
-        if stats:
-            return order, {f: int(getattr(out, f)) for f, _ in _SortStats._fields_}
-        return order
+        _check(self._lib.rj_scan_records_sort(self._h, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), n_records, _ptr(indices), k, _ptr(order),
+                                              ctypes.byref(out), ctypes.c_void_p(_stream(t.device, stream))))
+        return (order, _stats_dict(out)) if stats else order
 
     def lookup_records(self, set_text, set_begin, set_end, text, rec_begin, rec_end, set_indices=None, indices=None, hits=False, stats=False, stream=None):
         """rj_scan_records_lookup: the probe rows text[rec_begin[i], rec_end[i]) looked up in the set rows set_text[set_begin[i],
@@ -1030,34 +1036,23 @@ class Scan:
         import torch
 
         t = text
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
-        assert set_text.dtype == torch.uint8 and set_text.is_contiguous() and set_text.device == t.device
-        n_set_records, n_records = int(set_begin.numel()), int(rec_begin.numel())
-        for x, count in ((set_begin, n_set_records), (set_end, n_set_records), (rec_begin, n_records), (rec_end, n_records)):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == count
-
-        def rows(idx, every):
-            if idx is None:
-                return None, every
-            assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.device == t.device
-            if idx.numel() == 0:
-                return torch.zeros(1, dtype=torch.int64, device=t.device), 0   # (a non-null pointer: NULL means every record)
-            return idx, int(idx.numel())
-        set_indices, ks = rows(set_indices, n_set_records)
-        indices, kp = rows(indices, n_records)
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+        _check_text(t)
+        _check_text(set_text, t.device)
+        n_set_records = _check_table(set_begin, set_end, t.device)
+        n_records = _check_table(rec_begin, rec_end, t.device)
+        set_indices, ks = _rows(set_indices, n_set_records, t.device)
+        indices, kp = _rows(indices, n_records, t.device)
         index = torch.empty(kp, dtype=torch.int64, device=t.device)
         set_hits = torch.empty(ks, dtype=torch.int64, device=t.device) if hits else None
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
         out = _LookupStats()
-        _check(self._lib.rj_scan_records_lookup(self._h, ptr(set_text), int(set_text.numel()), ptr(set_begin), ptr(set_end), n_set_records, ptr(set_indices), ks,
-                                                ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), kp, ptr(index), ptr(set_hits),
-                                                ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
+        _check(self._lib.rj_scan_records_lookup(self._h, _ptr(set_text), int(set_text.numel()), _ptr(set_begin), _ptr(set_end), n_set_records, _ptr(set_indices),
+                                                ks, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), n_records, _ptr(indices), kp, _ptr(index),
+                                                _ptr(set_hits), ctypes.byref(out) if stats else None, ctypes.c_void_p(_stream(t.device, stream))))
         answer = (index,)
         if hits:
             answer += (set_hits,)
         if stats:
-            answer += ({f: int(getattr(out, f)) for f, _ in _LookupStats._fields_},)
+            answer += (_stats_dict(out),)
         return answer if len(answer) > 1 else index
 
     def parse_records(self, text_tensor, rec_begin, rec_end, indices=None, kind="int64", trim=False, stats=False, stream=None, wide=False):
@@ -1079,29 +1074,15 @@ class Scan:
         import torch
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        _check_text(t)
         if kind not in PARSE_KINDS:
             raise ValueError("parse_records: kind is 'int64', 'uint64' or 'float64', not %r" % (kind,))
-        n_records = int(rec_begin.numel())
-        for x in (rec_begin, rec_end):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
-        else:
-            k = n_records
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
-        values = torch.empty(k, dtype=torch.float64 if kind == "float64" else torch.int64, device=t.device)
-        status = torch.empty(k, dtype=torch.uint8, device=t.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
-        out = _ParseStats()
-        _check(self._lib.rj_scan_records_parse(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k, PARSE_KINDS[kind],
-                                               (PARSE_TRIM if trim else 0) | (PARSE_WIDE if wide else 0), ptr(values), ptr(status), ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
-        if stats:
-            return values, status, {f: int(getattr(out, f)) for f, _ in _ParseStats._fields_}
-        return values, status
+        flags = (PARSE_TRIM if trim else 0) | (PARSE_WIDE if wide else 0)
+
+        def call(n_records, rows, k, values, status, out, st):
+            return self._lib.rj_scan_records_parse(self._h, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), n_records, _ptr(rows), k, PARSE_KINDS[kind],
+                                                   flags, _ptr(values), _ptr(status), out, st)
+        return _parse_rows(call, t, rec_begin, rec_end, indices, torch.float64 if kind == "float64" else torch.int64, stats, stream)
 
     def parse_time_records(self, text_tensor, rec_begin, rec_end, fmt, indices=None, unit="s", trim=False, stats=False, stream=None):
         """rj_scan_records_parse_time: the rows text[rec_begin[i], rec_end[i]) -- all of them, or those `indices` names, as
@@ -1121,31 +1102,15 @@ class Scan:
         import torch
 
         t = text_tensor
-        assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda
+        _check_text(t)
         if unit not in TIME_UNITS:
             raise ValueError("parse_time_records: unit is 's', 'ms', 'us' or 'ns', not %r" % (unit,))
         fmt = fmt.encode("utf-8") if isinstance(fmt, str) else bytes(fmt)
-        n_records = int(rec_begin.numel())
-        for x in (rec_begin, rec_end):
-            assert x.dtype == torch.int64 and x.is_contiguous() and x.device == t.device and x.numel() == n_records
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == t.device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=t.device)   # (a non-null pointer: NULL means every record)
-        else:
-            k = n_records
-        st = torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
-        values = torch.empty(k, dtype=torch.int64, device=t.device)
-        status = torch.empty(k, dtype=torch.uint8, device=t.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
-        out = _ParseStats()
-        _check(self._lib.rj_scan_records_parse_time(self._h, ptr(t), int(t.numel()), ptr(rec_begin), ptr(rec_end), n_records, ptr(indices), k, fmt, len(fmt),
-                                                    TIME_UNITS[unit], PARSE_TRIM if trim else 0, ptr(values), ptr(status),
-                                                    ctypes.byref(out) if stats else None, ctypes.c_void_p(st)))
-        if stats:
-            return values, status, {f: int(getattr(out, f)) for f, _ in _ParseStats._fields_}
-        return values, status
+
+        def call(n_records, rows, k, values, status, out, st):
+            return self._lib.rj_scan_records_parse_time(self._h, _ptr(t), int(t.numel()), _ptr(rec_begin), _ptr(rec_end), n_records, _ptr(rows), k, fmt, len(fmt),
+                                                        TIME_UNITS[unit], PARSE_TRIM if trim else 0, _ptr(values), _ptr(status), out, st)
+        return _parse_rows(call, t, rec_begin, rec_end, indices, torch.int64, stats, stream)
 
     def format_records(self, values, kind=None, status=None, indices=None, fill: int = 10, lead: int = 0, gap: int = 1, out=None, stream=None, flags: int = 0):
         """rj_scan_records_format: the inverse of parse_records -- a column of numbers written as decimal text on the device,
@@ -1169,34 +1134,17 @@ class Scan:
         assert v.dtype == (torch.float64 if kind == "float64" else torch.int64)
         n_values = int(v.numel())
         if status is not None:
-            assert status.dtype == torch.uint8 and status.is_contiguous() and status.device == v.device and status.numel() == n_values
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == v.device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=v.device)   # (a non-null pointer: NULL means every value)
-        else:
-            k = n_values
-        st = torch.cuda.current_stream(v.device).cuda_stream if stream is None else stream
+            _check_column(status, torch.uint8, v.device, n_values)
+        indices, k = _rows(indices, n_values, v.device)
+        st = _stream(v.device, stream)
         out_begin = torch.empty(k, dtype=torch.int64, device=v.device)
         out_end = torch.empty(k, dtype=torch.int64, device=v.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
 
         def call(buf, cap):
-            return int(_check(self._lib.rj_scan_records_format(self._h, ptr(v), ptr(status), n_values, ptr(indices), k, PARSE_KINDS[kind], int(flags),
-                                                               int(fill), int(lead), int(gap), ptr(buf) if cap else None, cap, ptr(out_begin), ptr(out_end),
+            return int(_check(self._lib.rj_scan_records_format(self._h, _ptr(v), _ptr(status), n_values, _ptr(indices), k, PARSE_KINDS[kind], int(flags),
+                                                               int(fill), int(lead), int(gap), _ptr(buf), cap, _ptr(out_begin), _ptr(out_end),
                                                                ctypes.c_void_p(st))))
-        if out is None:
-            total = call(None, 0)
-            out = torch.empty(total, dtype=torch.uint8, device=v.device)
-            if total:
-                call(out, total)
-            return out, out_begin, out_end
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == v.device
-        total = call(out, int(out.numel()))
-        if total > out.numel():
-            raise RejitError(-4, "format_records: the text has %d bytes, `out` %d" % (total, out.numel()))
-        return out[:total], out_begin, out_end
+        return _sized_text(call, out, v.device, "format_records", "the text"), out_begin, out_end
 
     def format_time_records(self, values, fmt, unit="s", status=None, indices=None, zone_minutes: int = 0, fill: int = 10, lead: int = 0, gap: int = 1, out=None,
                             stream=None, stats=False):
@@ -1222,36 +1170,19 @@ class Scan:
         fmt = fmt.encode("utf-8") if isinstance(fmt, str) else bytes(fmt)
         n_values = int(v.numel())
         if status is not None:
-            assert status.dtype == torch.uint8 and status.is_contiguous() and status.device == v.device and status.numel() == n_values
-        if indices is not None:
-            assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == v.device
-            k = int(indices.numel())
-            if k == 0:
-                indices = torch.zeros(1, dtype=torch.int64, device=v.device)   # (a non-null pointer: NULL means every value)
-        else:
-            k = n_values
-        st = torch.cuda.current_stream(v.device).cuda_stream if stream is None else stream
+            _check_column(status, torch.uint8, v.device, n_values)
+        indices, k = _rows(indices, n_values, v.device)
+        st = _stream(v.device, stream)
         out_begin = torch.empty(k, dtype=torch.int64, device=v.device)
         out_end = torch.empty(k, dtype=torch.int64, device=v.device)
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)
         counts = _FormatTimeStats()
 
         def call(buf, cap):
-            return int(_check(self._lib.rj_scan_records_format_time(self._h, ptr(v), ptr(status), n_values, ptr(indices), k, fmt, len(fmt), TIME_UNITS[unit],
-                                                                    int(zone_minutes), 0, int(fill), int(lead), int(gap), ptr(buf) if cap else None, cap,
-                                                                    ptr(out_begin), ptr(out_end), ctypes.byref(counts), ctypes.c_void_p(st))))
-        result = lambda text: (text, out_begin, out_end) + (({f: int(getattr(counts, f)) for f, _ in _FormatTimeStats._fields_},) if stats else ())
-        if out is None:
-            total = call(None, 0)
-            out = torch.empty(total, dtype=torch.uint8, device=v.device)
-            if total:
-                call(out, total)
-            return result(out)
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == v.device
-        total = call(out, int(out.numel()))
-        if total > out.numel():
-            raise RejitError(-4, "format_time_records: the text has %d bytes, `out` %d" % (total, out.numel()))
-        return result(out[:total])
+            return int(_check(self._lib.rj_scan_records_format_time(self._h, _ptr(v), _ptr(status), n_values, _ptr(indices), k, fmt, len(fmt), TIME_UNITS[unit],
+                                                                    int(zone_minutes), 0, int(fill), int(lead), int(gap), _ptr(buf), cap, _ptr(out_begin),
+                                                                    _ptr(out_end), ctypes.byref(counts), ctypes.c_void_p(st))))
+        text = _sized_text(call, out, v.device, "format_time_records", "the text")
+        return (text, out_begin, out_end, _stats_dict(counts)) if stats else (text, out_begin, out_end)
 
     def zip_records(self, columns, sep: bytes = b"", widths=None, pad: int = 32, fill: int = 10, lead: int = 0, gap: int = 1, out=None, stream=None,
                     flags: int = 0):
@@ -1270,52 +1201,17 @@ class Scan:
         widths = [0] * len(columns) if widths is None else [int(w) for w in widths]
         if len(widths) != len(columns):
             raise ValueError("zip_records: %d widths for %d columns" % (len(widths), len(columns)))
-        if not columns:
-            raise RejitError(-4, "zip_records: no columns (a call takes 1 to 16)")
+        cols, k, keep = _zip_columns(columns, widths, "zip_records")   # (`keep` lives until the calls below have returned)
         sep = bytes(sep)
         device = columns[0][0].device
-        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else 0
-        cols = (ZipColumn * len(columns))()
-        keep = []
-        k = None
-        for c, column in enumerate(columns):
-            if len(column) not in (3, 4):
-                raise ValueError("zip_records: a column is (text, rec_begin, rec_end) or (text, rec_begin, rec_end, indices)")
-            t, rb, re_ = column[:3]
-            indices = column[3] if len(column) == 4 else None
-            assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda and t.device == device
-            n_records = int(rb.numel())
-            for x in (rb, re_):
-                assert x.dtype == torch.int64 and x.is_contiguous() and x.device == device and x.numel() == n_records
-            rows = n_records
-            if indices is not None:
-                assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == device
-                rows = int(indices.numel())
-                if rows == 0:
-                    indices = torch.zeros(1, dtype=torch.int64, device=device)   # (a non-null pointer: NULL means every record)
-                    keep.append(indices)
-            k = rows if k is None else k
-            cols[c] = ZipColumn(ptr(t), int(t.numel()), ptr(rb), ptr(re_), n_records, indices.data_ptr() if indices is not None else 0,
-                                rows if indices is not None else 0, widths[c], 0)
-        st = torch.cuda.current_stream(device).cuda_stream if stream is None else stream
+        st = _stream(device, stream)
         out_begin = torch.empty(k, dtype=torch.int64, device=device)
         out_end = torch.empty(k, dtype=torch.int64, device=device)
 
         def call(buf, cap):
             return int(_check(self._lib.rj_scan_records_zip(self._h, cols, len(columns), sep, len(sep), int(pad), int(flags), int(fill), int(lead), int(gap),
-                                                            ctypes.c_void_p(ptr(buf)) if cap else None, cap, ctypes.c_void_p(ptr(out_begin)),
-                                                            ctypes.c_void_p(ptr(out_end)), ctypes.c_void_p(st))))
-        if out is None:
-            total = call(None, 0)
-            out = torch.empty(total, dtype=torch.uint8, device=device)
-            if total:
-                call(out, total)
-            return out, out_begin, out_end
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == device
-        total = call(out, int(out.numel()))
-        if total > out.numel():
-            raise RejitError(-4, "zip_records: the text has %d bytes, `out` %d" % (total, out.numel()))
-        return out[:total], out_begin, out_end
+                                                            _ptr(buf), cap, _ptr(out_begin), _ptr(out_end), ctypes.c_void_p(st))))
+        return _sized_text(call, out, device, "zip_records", "the text"), out_begin, out_end
 
     def format_csv_records(self, columns, delimiter: bytes = b",", quote: bytes = b'"', always=(), raw=(), fill: int = 10, lead: int = 0, gap: int = 1,
                            out=None, stream=None, stats: bool = False, flags: int = 0):
@@ -1332,62 +1228,22 @@ class Scan:
         import torch
 
         columns = [tuple(c) for c in columns]
-        if not columns:
-            raise RejitError(-4, "format_csv_records: no columns (a call takes 1 to 16)")
-        byte = lambda x, name: int(x) if isinstance(x, int) else (bytes(x)[0] if len(bytes(x)) == 1 else _raise(ValueError("format_csv_records: %s is not one byte" % name)))
-        delimiter, quote = byte(delimiter, "delimiter"), byte(quote, "quote")
+        cols, k, keep = _zip_columns(columns, [0] * len(columns), "format_csv_records")   # (`keep` lives until the calls below have returned)
+        delimiter, quote = _one_byte(delimiter, "format_csv_records", "delimiter"), _one_byte(quote, "format_csv_records", "quote")
         mask = lambda listed, name: sum({1 << (int(c) if 0 <= int(c) < 32 else _raise(ValueError("format_csv_records: %s names column %d" % (name, c)))) for c in listed})
         always_mask, raw_mask = mask(always, "always"), mask(raw, "raw")
         device = columns[0][0].device
-        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else 0
-        cols = (ZipColumn * len(columns))()
-        keep = []
-        k = None
-        for c, column in enumerate(columns):
-            if len(column) not in (3, 4):
-                raise ValueError("format_csv_records: a column is (text, rec_begin, rec_end) or (text, rec_begin, rec_end, indices)")
-            t, rb, re_ = column[:3]
-            indices = column[3] if len(column) == 4 else None
-            assert t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda and t.device == device
-            n_records = int(rb.numel())
-            for x in (rb, re_):
-                assert x.dtype == torch.int64 and x.is_contiguous() and x.device == device and x.numel() == n_records
-            rows = n_records
-            if indices is not None:
-                assert indices.dtype == torch.int64 and indices.is_contiguous() and indices.device == device
-                rows = int(indices.numel())
-                if rows == 0:
-                    indices = torch.zeros(1, dtype=torch.int64, device=device)   # (a non-null pointer: NULL means every record)
-                    keep.append(indices)
-            k = rows if k is None else k
-            cols[c] = ZipColumn(ptr(t), int(t.numel()), ptr(rb), ptr(re_), n_records, indices.data_ptr() if indices is not None else 0,
-                                rows if indices is not None else 0, 0, 0)
-        st = torch.cuda.current_stream(device).cuda_stream if stream is None else stream
+        st = _stream(device, stream)
         out_begin = torch.empty(k, dtype=torch.int64, device=device)
         out_end = torch.empty(k, dtype=torch.int64, device=device)
         cs = _CsvFormatStats()
 
         def call(buf, cap):
             return int(_check(self._lib.rj_scan_records_format_csv(self._h, cols, len(columns), delimiter, quote, always_mask, raw_mask, int(flags), int(fill),
-                                                                   int(lead), int(gap), ctypes.c_void_p(ptr(buf)) if cap else None, cap,
-                                                                   ctypes.c_void_p(ptr(out_begin)), ctypes.c_void_p(ptr(out_end)),
+                                                                   int(lead), int(gap), _ptr(buf), cap, _ptr(out_begin), _ptr(out_end),
                                                                    ctypes.byref(cs) if stats else None, ctypes.c_void_p(st))))
-
-        def result(text):
-            if not stats:
-                return text, out_begin, out_end
-            return text, out_begin, out_end, {f: int(getattr(cs, f)) for f, _ in _CsvFormatStats._fields_}
-        if out is None:
-            total = call(None, 0)
-            out = torch.empty(total, dtype=torch.uint8, device=device)
-            if total:
-                call(out, total)
-            return result(out)
-        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == device
-        total = call(out, int(out.numel()))
-        if total > out.numel():
-            raise RejitError(-4, "format_csv_records: the text has %d bytes, `out` %d" % (total, out.numel()))
-        return result(out[:total])
+        text = _sized_text(call, out, device, "format_csv_records", "the text")
+        return (text, out_begin, out_end, _stats_dict(cs)) if stats else (text, out_begin, out_end)
 
     def replace(self, d_text_ptr: int, n: int, repl: bytes, d_out_ptr: int, out_cap: int, stream: int = 0) -> int:
         """Replace the matches of the last run(); returns the new length (text stays in HBM)."""
